@@ -925,6 +925,15 @@ def extra_euler_beam(tmp, epochs=2000):
 
 
 # ------------------------------------------------------------------------------------------------------ main
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy (float32; float64 stays float64), for comparing two builds output
+    for output.  The primary workload's results are small (4 x 12 929 floats + the loss terms): written whole."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main():
     # stdout carries exactly ONE line, the JSON record: everything else this process prints (the ppsci logger of the API-level
     # entries writes to sys.stdout, as the reference's does) goes to stderr
@@ -940,7 +949,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the cfg 1/3/4/5 entries (N = 1 only anyway)")
     ap.add_argument("--no-strong", action="store_true", help="skip the 1 M-point NavierStokes strong-scaling entry")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (weights, gradient, Adam moments, loss "
+                         "terms) as DIR/<name>.npy")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps: at least one timed step"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU) through
@@ -1008,33 +1021,53 @@ def main():
     g0, loss0 = eng.grad.detach().cpu().numpy().copy(), cst.losses()["allen_cahn"]
     eng.train_step([cst], 1e-3)  # (plans the step)
     fused = cst.one_launch_ready() and getattr(cst, "_step_kind", 0) == hp.STEP_FUSED_TILE and eng.one_launch
-    # Timing.  `--steps K` is ONE window: K steps between barrier + synchronize; WINDOWS such windows
-    # run back to back behind the W warm-up steps, `ms_per_step` is the MEDIAN window (min / max printed next to it: boxes
-    # and clock states differ by several per cent over a 5 ms window).  The kernel-level figure of the roofline entry is
-    # taken with HIP events on the launch stream BETWEEN the windows -- six launches of the main kernel alone after each --
-    # i.e. in the same sustained clock state as the steps it is compared with, not on the clock ramp behind the idle phase
-    # of the parity legs (round 5 printed kernel_ms 0.2329 > ms_per_step 0.2269 that way).
+    # Timing.  `--steps K` is the number of timed steps: K steps back to back behind the W warm-up
+    # steps, between one barrier + synchronize before and one after.  HIP events on the launch stream cut them into WINDOWS
+    # consecutive windows (at most 10; no host synchronisation between them), and `ms_per_step` is the MEDIAN window's time
+    # per step (min / max printed next to it: boxes and clock states differ by several per cent over a 5 ms window, and the
+    # first steps after the idle phase of the parity legs run on the clock ramp).  The kernel-level figure of the roofline
+    # entry is taken with HIP events right behind the timed steps -- six launches of the main kernel alone per window --
+    # i.e. in the same sustained clock state as the steps it is compared with (round 5 printed kernel_ms 0.2329 >
+    # ms_per_step 0.2269 when it was taken in front of them).
     # (The full garbage collection of quiet_host -- tens of ms of host time with the GPU idle -- sits in front of the warm-up.)
-    WINDOWS = 1 if EMU else 10
-    wins, main_samples = [], []
+    WINDOWS = 1 if EMU else min(10, args.steps)
+    sizes = [args.steps // WINDOWS + (i < args.steps % WINDOWS) for i in range(WINDOWS)]
+    # window boundaries: the host clock on the emulator (it runs synchronously), HIP events on the launch stream otherwise
+    marks = [0.0] * (WINDOWS + 1) if EMU else [torch.cuda.Event(enable_timing=True) for _ in range(WINDOWS + 1)]
+
+    def mark(i):
+        if EMU:
+            marks[i] = time.perf_counter()
+        else:
+            marks[i].record()
+
+    last = None
     with quiet_host():
         t_res = time_events(lambda: cst.forward(params, False), 30, median=True)
         for _ in range(args.warmup):
             eng.train_step([cst], 1e-3)
-        for _ in range(WINDOWS):
-            barrier()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
+        barrier()
+        mark(0)
+        for i, k in enumerate(sizes):
+            for _ in range(k):
                 eng.train_step([cst], 1e-3)
-            barrier()
-            wins.append(time.perf_counter() - t0)
-            if fused and not EMU:
-                main_samples += time_events_list(cst._step_plan.run_main, 6)
+            mark(i + 1)
+        barrier()
+        wins = [((marks[i + 1] - marks[i]) if EMU else marks[i].elapsed_time(marks[i + 1]) * 1e-3) / k
+                for i, k in enumerate(sizes)]
+        if args.dump_outputs and rank == 0:
+            # (copies of the last step's results before the kernel-only launches below reuse the plan's buffers)
+            last = {"params": eng.params, "grad": eng.grad, "adam_m": eng.m, "adam_v": eng.v, "loss_terms": cst.loss_terms}
+            last = {name: t.detach().clone() for name, t in last.items()}
+        main_samples = time_events_list(cst._step_plan.run_main, 6 * WINDOWS) if fused and not EMU else []
+    assert sum(sizes) == args.steps
     tt = torch.tensor(wins, device=dev, dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)  # every window: the slowest rank
-    wins = sorted(tt.cpu().tolist())
+    wins = sorted(tt.cpu().tolist())  # seconds per step, per window
     dt = wins[(len(wins) - 1) // 2]  # the median window (lower median for an even count)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
     t_main = (float(np.median(main_samples)) if main_samples else time_events(cst._step_plan.run_main, 1)) if fused else None
     loss = cst.losses()["allen_cahn"]
 
@@ -1065,7 +1098,7 @@ def main():
 
     # HBM traffic of the dominant kernel per launch and of the whole step: quoted from the newest committed rocprofv3
     # summary (tools/profile_bench.sh; separate --pmc passes, FETCH_SIZE doubled per MI355X_MICROARCH.md) with its file name
-    prof = profile_info("bench", ksub, dt / args.steps * 1e3, once_per_step=True)
+    prof = profile_info("bench", ksub, dt * 1e3, once_per_step=True)
     traffic, traffic_src = prof.get("kernel_hbm_bytes_per_launch"), prof.get("source")
 
     strong = None
@@ -1084,13 +1117,13 @@ def main():
     if rank == 0:
         out = {
             "metric": "collocation-points/sec (PDE residual+grad)",
-            "value": N_PER_GPU * world * args.steps / dt,
+            "value": N_PER_GPU * world / dt,
             "unit": "points/s",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_min": wins[0] / args.steps * 1e3, "ms_per_step_max": wins[-1] / args.steps * 1e3,
+            "ms_per_step": dt * 1e3,
+            "ms_per_step_min": wins[0] * 1e3, "ms_per_step_max": wins[-1] * 1e3,
             "windows": len(wins),
             "higher_is_better": True,
             "scaling": "weak",
