@@ -233,6 +233,14 @@ int ppsci_epilogue(const ppsci_epilogue_desc* e, int64_t n_points, const float* 
 int ppsci_dense_matvec(int64_t rows, int64_t cols, const float* M, const float* x, const float* rowscale, float alpha,
                        int transpose, float* y, void* stream);
 
+/* The same map stored sparse (the fractional Laplacian of ppsci/equation/fpde/fractional_poisson.py:57-82: ~690 nonzeros per
+ * row, one per column).  CSR with int32 indices on the device: row_ptr [rows + 1], col_idx / vals [nnz], col_idx < cols.
+ *   y[i] = alpha * sum_{k in row i} vals[k] * x[col_idx[k]] * xscale[col_idx[k]]      (i < rows; xscale NULL = 1)
+ * The transposed product is this call on the CSR of M^T.  One lane writes each y[i], summing in an order fixed by the matrix
+ * (no atomics: bitwise reproducible).  rows <= 2^30, cols and nnz < 2^31, else PPSCI_E_INVALID. */
+int ppsci_csr_matvec(int64_t rows, int64_t cols, int64_t nnz, const int32_t* row_ptr, const int32_t* col_idx,
+                     const float* vals, const float* x, const float* xscale, float alpha, float* y, void* stream);
+
 /* ppsci_epilogue for programs that read learnable equation parameters (PPSCI_OP_LD_PARAM; e.g. the damping and
  * stiffness exponents of equation/pde/viv.py:41-62): eq_params: [PPSCI_MAX_EPARAM] current values (+ a second block of
  * PPSCI_MAX_EPARAM term multipliers when a residual sets `scale_param`) (broadcast over

@@ -64,6 +64,15 @@ def _to_dev(a, dev) -> torch.Tensor:
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(dev).contiguous().view(-1)
 
 
+def _csr_to_dev(M, dev) -> dict:
+    """A graph.CsrMatrix coupling on the device: the CSR arrays of M and of M^T (engine.FusedConstraint._forward_couplings)."""
+    def up(m):
+        return dict(row_ptr=torch.from_numpy(m.row_ptr).to(dev), col_idx=torch.from_numpy(m.col_idx).to(dev),
+                    vals=torch.from_numpy(m.vals).to(dev), cols=m.shape[1])
+
+    return dict(M=up(M), MT=up(M.transpose()))
+
+
 class CompiledConstraint:
     """A constraint (or validator) bound to the fused kernels for a fixed batch size."""
 
@@ -176,7 +185,11 @@ class CompiledConstraint:
             if self.low.periodic or self.low.causal or self._row_slices:
                 raise NotImplementedError("batch couplings together with a periodic / causal loss or row-sliced outputs")
             cpl = self.low.couplings
-            mats = [torch.as_tensor(graph._COUPLE_MATS[it["name"]]).to(dev) for it in cpl["items"]]
+            mats = []
+            for it in cpl["items"]:
+                M = graph.take_coupling(it["name"])
+                # sparse: M and M^T uploaded once as device CSR (the transposed product is a CSR product of its own)
+                mats.append(_csr_to_dev(M, dev) if isinstance(M, graph.CsrMatrix) else torch.as_tensor(M).to(dev))
             self.fused.set_couplings(cpl["items"], cpl["pv"].build(), cpl["p3"].build(), mats)
         if self.low.reductions:
             if self.low.periodic or self.low.causal or self._row_slices:

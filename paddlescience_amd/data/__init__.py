@@ -14,6 +14,7 @@ import numpy as np
 from ..utils import logger
 from . import dataset
 from .dataset import build_dataset  # noqa: F401
+from .process import transform  # noqa: F401
 
 
 def _world():

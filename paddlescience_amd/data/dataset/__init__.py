@@ -16,5 +16,10 @@ def build_dataset(cfg):
     cls = cfg.pop("name")
     if cls not in __all__[:-1]:
         raise NotImplementedError(f"dataset {cls!r} (file-backed data-driven datasets are out of scope of the PINN hot path)")
-    cfg.pop("transforms", None) if cfg.get("transforms") is None else None
+    if "transforms" in cfg:  # dataset/__init__.py:105-106: a config list becomes a callable
+        from ..process import transform
+
+        cfg["transforms"] = transform.build_transforms(cfg.pop("transforms"))
+        if cfg["transforms"] is None:
+            cfg.pop("transforms")
     return globals()[cls](**cfg)

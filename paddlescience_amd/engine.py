@@ -144,7 +144,8 @@ class FusedConstraint:
 
     def set_couplings(self, items: Sequence[dict], pv: L.EpilogueDesc, p3: L.EpilogueDesc, matrices: Sequence[torch.Tensor]) -> None:
         """Batch-coupled residuals lhs[:R] - M v (graph.couple; ppsci/equation/ide/volterra.py:66-77): `pv` evaluates every v into
-        a row of `_cv`, `p3` is the residual program + one LINEAR term per coupling on v with the per-point weight column vbar."""
+        a row of `_cv`, `p3` is the residual program + one LINEAR term per coupling on v with the per-point weight column vbar.
+        A matrix is a dense [R, N] tensor or a dict of device CSR arrays of M and M^T (compile._csr_to_dev)."""
         f32 = dict(dtype=torch.float32, device=self.U.device)
         assert self.resid is not None
         self.couplings = dict(items=list(items), pv=pv, p3=p3, M=list(matrices))
@@ -158,15 +159,22 @@ class FusedConstraint:
         cp, n = self.couplings, self.n
         hp.epilogue(cp["pv"], n, self.inputs, self.U, self.aux, self._cv, None, self._cl1)
         for j, (it, M) in enumerate(zip(cp["items"], cp["M"])):
-            hp.dense_matvec(M, self._cv[j], self.aux[it["rhs_aux"]], 1.0, False)
+            if isinstance(M, dict):
+                hp.csr_matvec(**M["M"], x=self._cv[j], y=self.aux[it["rhs_aux"]], alpha=it["factor"])
+            else:
+                hp.dense_matvec(M, self._cv[j], self.aux[it["rhs_aux"]], it["factor"], False)
         hp.epilogue(self.edesc, n, self.inputs, self.U, self.aux, self.resid, self.Ubar if train else None, self.loss_partials)
         hp.reduce_rows(self.loss_partials, self.loss_rows, max(1, self.edesc.n_res), self.loss_terms, False)
         if not train:
             return
         for it, M in zip(cp["items"], cp["M"]):
             scale = float(self.edesc.res[it["res_row"]].scale)
-            hp.dense_matvec(M, self.resid[it["res_row"]], self.aux[it["vbar_aux"]], -2.0 * scale, True,
-                            rowscale=self.aux[it["weight_aux"]])
+            if isinstance(M, dict):  # vbar = -c M^T (2 scale w d): the CSR product of M^T, w as the scale of its columns
+                hp.csr_matvec(**M["MT"], x=self.resid[it["res_row"]], y=self.aux[it["vbar_aux"]],
+                              alpha=-2.0 * scale * it["factor"], xscale=self.aux[it["weight_aux"]])
+            else:
+                hp.dense_matvec(M, self.resid[it["res_row"]], self.aux[it["vbar_aux"]], -2.0 * scale * it["factor"], True,
+                                rowscale=self.aux[it["weight_aux"]])
         hp.epilogue(cp["p3"], n, self.inputs, self.U, self.aux, None, self.Ubar, self._cl3)
 
     def set_causal(self, rows: Sequence[tuple], n_chunks: int, tol: float) -> None:

@@ -16,6 +16,7 @@ computes numerically (ad.py:73-75).
 from __future__ import annotations
 
 import contextlib
+import itertools
 import zlib
 import math
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
@@ -385,17 +386,80 @@ def concrete_values(s: "Sym", what: str = "value") -> np.ndarray:
 # `lhs[:len(rhs)] - paddle.mm(int_mat, v)` (ppsci/equation/ide/volterra.py:66-77): rows i < R of the batch get the residual
 # lhs_i - sum_q M[i, q] v_q, the other rows (the quadrature points) carry no residual.  Only legal as a WHOLE output expression:
 # lower() turns it into a per-point program around two small matrix-vector launches (engine.FusedConstraint._forward_couplings).
+# M is dense (Volterra: a few hundred entries) or a CsrMatrix (the fractional Laplacian, ppsci/equation/fpde/
+# fractional_poisson.py:57-82: ~690 nonzeros per row of 100 k to 1.4 M columns), and may carry a scalar factor c (the residual is
+# lhs - c M v, the factor applied by the kernel's alpha, not rounded into the entries).  The matrices wait here between the
+# trace and the upload of the compiled constraint, which takes them out (CompiledConstraint: `take_coupling`).
 COUPLE_RHS_PREFIX, COUPLE_VBAR_PREFIX = "__couple_rhs__", "__couple_vbar__"
-_COUPLE_MATS: Dict[str, np.ndarray] = {}
+_COUPLE_MATS: Dict[str, object] = {}
+_COUPLE_SEQ = itertools.count()
 
 
-def couple(lhs, matrix, v) -> "Sym":
-    M = np.ascontiguousarray(np.asarray(matrix, dtype=np.float32))
-    if M.ndim != 2:
-        raise ValueError(f"couple(): a [rows, batch] matrix is needed, got shape {M.shape}")
-    name = f"couple{len(_COUPLE_MATS)}_{zlib.crc32(M.tobytes()):08x}"
+class CsrMatrix:
+    """A constant [rows, cols] float32 matrix in CSR with int32 indices, checked on the host (the kernel trusts the indices)."""
+
+    def __init__(self, row_ptr, col_idx, vals, shape):
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.row_ptr = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64))
+        self.col_idx = np.ascontiguousarray(np.asarray(col_idx, dtype=np.int64))
+        self.vals = np.ascontiguousarray(np.asarray(vals, dtype=np.float32))
+        rows, cols = self.shape
+        nnz = len(self.vals)
+        if rows <= 0 or cols <= 0 or len(self.row_ptr) != rows + 1 or len(self.col_idx) != nnz:
+            raise ValueError(f"CsrMatrix: inconsistent CSR arrays for shape {self.shape}")
+        if nnz >= 2 ** 31 or cols >= 2 ** 31:
+            raise ValueError(f"CsrMatrix: {nnz} nonzeros / {cols} columns exceed int32 indices")
+        if self.row_ptr[0] != 0 or self.row_ptr[-1] != nnz or np.any(np.diff(self.row_ptr) < 0):
+            raise ValueError("CsrMatrix: row_ptr must rise from 0 to nnz")
+        if nnz and (self.col_idx.min() < 0 or self.col_idx.max() >= cols):
+            raise ValueError(f"CsrMatrix: a column index outside [0, {cols})")
+        self.row_ptr, self.col_idx = self.row_ptr.astype(np.int32), self.col_idx.astype(np.int32)
+
+    @property
+    def nnz(self) -> int:
+        return len(self.vals)
+
+    @staticmethod
+    def from_coo(rows, cols, vals, shape) -> "CsrMatrix":
+        """Entries sorted by row; within a row they keep their given order (which is the summation order)."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        order = np.argsort(rows, kind="stable")
+        ptr = np.zeros(int(shape[0]) + 1, np.int64)
+        np.cumsum(np.bincount(rows, minlength=int(shape[0])), out=ptr[1:])
+        return CsrMatrix(ptr, np.asarray(cols, np.int64).reshape(-1)[order], np.asarray(vals, np.float32).reshape(-1)[order],
+                         shape)
+
+    def row_of_entries(self) -> np.ndarray:
+        return np.repeat(np.arange(self.shape[0], dtype=np.int64), np.diff(self.row_ptr))
+
+    def transpose(self) -> "CsrMatrix":
+        """M^T in CSR; row q of it lists the entries of column q of M by increasing row (the dense transposed order)."""
+        return CsrMatrix.from_coo(self.col_idx, self.row_of_entries(), self.vals, (self.shape[1], self.shape[0]))
+
+    def crc(self) -> int:
+        c = zlib.crc32(self.row_ptr.tobytes())
+        c = zlib.crc32(self.col_idx.tobytes(), c)
+        return zlib.crc32(self.vals.tobytes(), c)
+
+
+def couple(lhs, matrix, v, factor: Optional[float] = None) -> "Sym":
+    """lhs - factor * (M v) on the first M.shape[0] rows of the batch; `matrix` is a [rows, batch] array or a CsrMatrix."""
+    if isinstance(matrix, CsrMatrix):
+        M, crc = matrix, matrix.crc()
+    else:
+        M = np.ascontiguousarray(np.asarray(matrix, dtype=np.float32))
+        if M.ndim != 2:
+            raise ValueError(f"couple(): a [rows, batch] matrix is needed, got shape {M.shape}")
+        crc = zlib.crc32(M.tobytes())
+    name = f"couple{next(_COUPLE_SEQ)}_{crc:08x}"
     _COUPLE_MATS[name] = M
-    return Sym("couple", name=name, comp=(int(M.shape[0]), int(M.shape[1])), args=(_lift(lhs), _lift(v)))
+    return Sym("couple", name=name, value=None if factor is None else float(factor), comp=(int(M.shape[0]), int(M.shape[1])),
+               args=(_lift(lhs), _lift(v)))
+
+
+def take_coupling(name: str):
+    """The matrix of coupling `name`, removed from the registry (the caller uploads it once)."""
+    return _COUPLE_MATS.pop(name)
 
 
 def _lift(v) -> Sym:
@@ -920,6 +984,7 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
             p3.residual(val[id(c.args[1])], -1, vb, -1, 1.0, hp.LOSS_LINEAR)
             row, w = couple_rows[c.name]
             items.append({"name": c.name, "rows": c.comp[0], "cols": c.comp[1], "res_row": row, "weight_aux": w,
+                          "factor": 1.0 if c.value is None else c.value,
                           "rhs_aux": aux_names.index(COUPLE_RHS_PREFIX + c.name), "vbar_aux": vb})
         low.aux_names = aux_names
         low.couplings = {"items": items, "pv": pv, "p3": p3}

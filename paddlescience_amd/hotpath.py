@@ -281,6 +281,22 @@ def dense_matvec(M: torch.Tensor, x: torch.Tensor, y: torch.Tensor, alpha: float
                                        _stream_ptr(y)))
 
 
+def csr_matvec(row_ptr: torch.Tensor, col_idx: torch.Tensor, vals: torch.Tensor, cols: int, x: torch.Tensor, y: torch.Tensor,
+               alpha: float = 1.0, xscale: Optional[torch.Tensor] = None) -> None:
+    """ppsci_csr_matvec: y[:rows] = alpha M (x * xscale), M [rows, cols] in CSR (int32 row_ptr [rows + 1] and col_idx [nnz],
+    float32 vals [nnz]).  The column indices are trusted: they are checked on the host where the matrix is built
+    (graph.CsrMatrix)."""
+    _require_device(y)
+    _chk_f32(vals, x, y, xscale)
+    for t in (row_ptr, col_idx):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("CSR indices must be contiguous int32 tensors")
+    rows, nnz = row_ptr.numel() - 1, vals.numel()
+    assert col_idx.numel() == nnz and x.numel() >= cols and y.numel() >= rows and (xscale is None or xscale.numel() >= cols)
+    L.check(L.lib().ppsci_csr_matvec(rows, cols, nnz, _p(row_ptr), _p(col_idx), _p(vals), _p(x), _p(xscale), float(alpha), _p(y),
+                                     _stream_ptr(y)))
+
+
 def reduce_rows(partials: torch.Tensor, rows: int, cols: int, out: torch.Tensor, accumulate: bool) -> None:
     _require_device(out)
     _chk_f32(partials, out)
