@@ -751,9 +751,40 @@ int ppsci_pirate_act_bwd(int mode, int act, int H, int64_t N, int64_t NP, int n1
                          const float* bias, const float* U, const float* V, const float* x, const float* alpha,
                          const float* obar, float* zbar, float* Ubar, float* Vbar, float* xbar, float* partials_b,
                          float* partials_alpha, void* stream);
+/* Learnable swish x * sigmoid(beta x) (activation.py:49-58) is accepted in mode ACT only: `alpha` then points to the
+ * layer's scalar beta and, backward, `partials_alpha` receives the beta gradient as [H * chunks] partial values. */
 /* last_fc output Y [S][m][NP] (+ bias on the value stream) -> the U rows [m*S][N] of ppsci_epilogue, and back. */
 int ppsci_pirate_out_fwd(int S, int m, int64_t N, int64_t NP, const float* Y, const float* bias, float* U, void* stream);
 int ppsci_pirate_out_bwd(int S, int m, int64_t N, int64_t NP, const float* Ubar, float* Ybar, void* stream);
+
+/* ---- ppsci.arch.DeepONet / HEDeepONets / ChipDeepONets head (csrc/pirate.hip) ------------------------------------
+ * G_o = sum_{k < p} prod_j B_j[o p + k] * act(Z + tbias)[o p + k] + b[o]  (deeponet.py:129-154, he_deeponets.py:151-197,
+ * chip_deeponets.py:186-214) on the trunk's Taylor streams; the J branch features carry the value only. */
+#define PPSCI_ONET_MAX_J 3
+typedef struct ppsci_onet_head_desc {
+  int32_t J;          /* branch nets: 1 DeepONet, 2 HEDeepONets, 3 ChipDeepONets */
+  int32_t p;          /* num_features */
+  int32_t n_out;      /* outputs; F = p * n_out trunk / branch features */
+  int32_t n1, n2;     /* stream counts of the trunk: S = 1 + n1 + n2 */
+  int32_t act;        /* trunk_act: PPSCI_ACT_{TANH, SILU, SIGMOID, SIN, COS, GELU, SWISH} */
+  int64_t N, NP;      /* points; NP = padded plane length, a multiple of 16 */
+} ppsci_onet_head_desc;
+/* A branch key [N][m] (row-major) -> planar [m][NP] with zero padding: what ppsci_pw_conv reads (the concat of the
+ * branch net's input keys, mlp.py:314). */
+int ppsci_onet_pack(int m, int64_t N, int64_t NP, const float* src, float* dst, void* stream);
+/* Z [S][F][NP]: trunk last_fc output without its bias; B_host[j] [F][NP]: branch j last_fc output without its bias;
+ * bbias_host[j] [F]; beta: device scalar of a swish trunk_act; b [n_out] or NULL (use_bias = False).
+ * U [n_out * S][N]: the row layout of ppsci_pirate_out_fwd. */
+int ppsci_onet_head_fwd(const ppsci_onet_head_desc* d, const float* Z, const float* tbias, const float* const* B_host,
+                        const float* const* bbias_host, const float* beta, const float* b, float* U, void* stream);
+/* Reverse: Zbar [S][F][NP], Bbar_host[j] [F][NP]; partial rows, summed with ppsci_reduce_rows:
+ * trunk bias [chunks][F], branch biases [J][chunks][F], beta [F * chunks] (swish only), b [chunks][n_out] (or NULL),
+ * chunks = ppsci_onet_head_chunks(NP). */
+int64_t ppsci_onet_head_chunks(int64_t NP);
+int ppsci_onet_head_bwd(const ppsci_onet_head_desc* d, const float* Z, const float* tbias, const float* const* B_host,
+                        const float* const* bbias_host, const float* beta, const float* Ubar, float* Zbar,
+                        float* const* Bbar_host, float* partials_tbias, float* partials_bbias, float* partials_beta,
+                        float* partials_b, void* stream);
 
 /* Tensor-product grid: q(i,j,k) = sum_r fx[i,r] fy[j,r] fz[k,r] (SPINN.forward_tensor spinn.py:140-167) for
  * q in {u, u_xx, u_yy, u_zz}; res = cu*u + cxx*u_xx + cyy*u_yy + czz*u_zz (Helmholtz helmholtz.py:78-93:

@@ -76,6 +76,14 @@ class PirateEmbedDesc(C.Structure):
 PIRATE_ACT, PIRATE_GATE, PIRATE_RES = 0, 1, 2
 
 
+ONET_MAX_J = 3
+
+
+class OnetHeadDesc(C.Structure):  # ppsci_onet_head_desc
+    _fields_ = [("J", C.c_int32), ("p", C.c_int32), ("n_out", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
+                ("act", C.c_int32), ("N", C.c_int64), ("NP", C.c_int64)]
+
+
 class Instr(C.Structure):
     _fields_ = [("op", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("c", C.c_float)]
 
@@ -257,6 +265,13 @@ _SYMBOLS = {
     "ppsci_pirate_act_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 14),
     "ppsci_pirate_out_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppsci_pirate_out_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppsci_onet_pack": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppsci_onet_head_chunks": (C.c_int64, [C.c_int64]),
+    "ppsci_onet_head_fwd": (C.c_int, [C.POINTER(OnetHeadDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppsci_onet_head_bwd": (C.c_int, [C.POINTER(OnetHeadDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+                            + [C.c_void_p] * 5),
     "ppsci_spinn_grid_partial_rows": (C.c_int64, [C.POINTER(SpinnGridDesc)]),
     "ppsci_spinn_grid_fwd": (C.c_int, [C.POINTER(SpinnGridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

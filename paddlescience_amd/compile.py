@@ -161,8 +161,17 @@ class CompiledConstraint:
         self._stage_done: List[Optional[torch.cuda.Event]] = []
         self._flip = 0
         nets = []
+        # operator nets (arch/deeponet.py): every branch key is an [N, m] device tensor of its own, handed to the executor
+        # through the layout -- never a row of the block above (the epilogue program does not read it)
+        self._branch: Dict[str, torch.Tensor] = {}
         for m, spec, _, idx, pre in self.low.nets:
             lay = m.layout
+            cols = getattr(m, "branch_cols", None)
+            if cols:
+                for k, c in cols.items():
+                    if k not in self._branch:
+                        self._branch[k] = torch.zeros((batch_size, c), dtype=torch.float32, device=dev)
+                lay = lay.with_branch({k: self._branch[k] for k in cols})
             if pre is not None:  # input transform: every network input is an [S, N] stream block
                 import dataclasses
 
@@ -225,6 +234,12 @@ class CompiledConstraint:
                 srcs.append(None)  # written on the device every step (engine.FusedConstraint.forward)
             else:
                 srcs.append(input[name])
+        for k, dst in self._branch.items():
+            src = input[k]
+            src = src.detach() if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src, dtype=np.float32))
+            if int(src.shape[0]) != dst.shape[0] or src.numel() != dst.numel():
+                raise ValueError(f"branch key {k!r}: expected [{dst.shape[0]}, {dst.shape[1]}], got {tuple(src.shape)}")
+            dst.copy_(src.reshape(dst.shape).to(device=dst.device, dtype=torch.float32))
         if not self._block.is_cuda or any(isinstance(v, torch.Tensor) and v.is_cuda for v in srcs):
             for row, src in zip(self._block, srcs):
                 if src is not None:

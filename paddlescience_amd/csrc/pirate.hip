@@ -50,6 +50,17 @@ __device__ __forceinline__ void pr_act(int act, float z, float& s, float& d1, fl
   }
 }
 
+// value, three z-derivatives and (swish) the beta-derivatives of (s, d1, d2); `beta` is read only for swish
+__device__ __forceinline__ void pr_act_p(int act, float z, const float* beta, float& s, float& d1, float& d2, float& d3,
+                                         float& sp, float& d1p, float& d2p) {
+  if (act == PPSCI_ACT_SWISH) {
+    ppsci_act_eval_p<PPSCI_ACT_SWISH>(z, beta[0], s, d1, d2, d3, sp, d1p, d2p);
+  } else {
+    pr_act(act, z, s, d1, d2, d3);
+    sp = d1p = d2p = 0.f;
+  }
+}
+
 // fixed-shape tree sum over the workgroup; result valid in thread 0
 __device__ __forceinline__ float pr_block_sum(float v, float* red) {
   __syncthreads();
@@ -235,8 +246,8 @@ __global__ void __launch_bounds__(PR_BLOCK) pirate_act_fwd_kernel(PrActArgs a) {
     for (int s = 0; s < S; ++s) a.out[s * plane + e] = 0.f;
     return;
   }
-  float s0, d1, d2, d3;
-  pr_act(a.act, a.z[e] + a.bias[h], s0, d1, d2, d3);
+  float s0, d1, d2, d3, sp, d1p, d2p;
+  pr_act_p(a.act, a.z[e] + a.bias[h], a.alpha, s0, d1, d2, d3, sp, d1p, d2p);  // swish (mode ACT): alpha = &beta
   float ap[PPSCI_MAX_DIRS], app[PPSCI_MAX_DIRS];
   for (int q = 0; q < n1; ++q) {
     const float zp = a.z[(1 + q) * plane + e];
@@ -280,8 +291,8 @@ __global__ void __launch_bounds__(PR_BLOCK) pirate_act_bwd_kernel(PrActArgs a) {
       if (a.mode == PPSCI_PIRATE_RES) a.xbar[s * plane + e] = 0.f;
     }
   } else if (p < a.N) {
-    float s0, d1, d2, d3;
-    pr_act(a.act, a.z[e] + a.bias[h], s0, d1, d2, d3);
+    float s0, d1, d2, d3, sp, d1p, d2p;
+    pr_act_p(a.act, a.z[e] + a.bias[h], a.alpha, s0, d1, d2, d3, sp, d1p, d2p);
     float zp[PPSCI_MAX_DIRS], zpp[PPSCI_MAX_DIRS], ap[PPSCI_MAX_DIRS], app[PPSCI_MAX_DIRS];
     for (int q = 0; q < n1; ++q) {
       zp[q] = a.z[(1 + q) * plane + e];
@@ -338,6 +349,13 @@ __global__ void __launch_bounds__(PR_BLOCK) pirate_act_bwd_kernel(PrActArgs a) {
         }
       }
     }
+    if (a.act == PPSCI_ACT_SWISH) {  // d loss / d beta: the beta-derivatives of the activation streams
+      galpha = sp * ab0;
+      for (int q = 0; q < n1; ++q) {
+        galpha += d1p * zp[q] * ab1[q];
+        if (q < n2) galpha += (d2p * zp[q] * zp[q] + d1p * zpp[q]) * ab2[q];
+      }
+    }
     // adjoint of z's streams (Faa di Bruno, order 2)
     zb0 = d1 * ab0;
     for (int q = 0; q < n1; ++q) {
@@ -354,7 +372,7 @@ __global__ void __launch_bounds__(PR_BLOCK) pirate_act_bwd_kernel(PrActArgs a) {
   }
   const float sb = pr_block_sum(zb0, red);
   if (threadIdx.x == 0) a.pb[(long long)ch * a.H + h] = sb;
-  if (a.mode == PPSCI_PIRATE_RES) {
+  if (a.mode == PPSCI_PIRATE_RES || a.act == PPSCI_ACT_SWISH) {
     const float sa = pr_block_sum(galpha, red);
     if (threadIdx.x == 0) a.palpha[blockIdx.x] = sa;
   }
@@ -436,9 +454,13 @@ static int act_check(int mode, int act, int H, int64_t N, int64_t NP, int n1, in
     ppsci_set_error("pirate_act: invalid argument");
     return PPSCI_E_INVALID;
   }
+  if (act == PPSCI_ACT_SWISH && mode != PPSCI_PIRATE_ACT) {
+    ppsci_set_error("pirate_act: swish (trainable beta) only in mode ACT");
+    return PPSCI_E_INVALID;
+  }
   if (act != PPSCI_ACT_TANH && act != PPSCI_ACT_SILU && act != PPSCI_ACT_SIGMOID && act != PPSCI_ACT_COS &&
-      act != PPSCI_ACT_GELU && act != PPSCI_ACT_SIN) {
-    ppsci_set_error("pirate_act: activation %d has no PirateNet kernel (tanh, silu, sigmoid, sin, cos, gelu)", act);
+      act != PPSCI_ACT_GELU && act != PPSCI_ACT_SIN && act != PPSCI_ACT_SWISH) {
+    ppsci_set_error("pirate_act: activation %d has no PirateNet kernel (tanh, silu, sigmoid, sin, cos, gelu, swish)", act);
     return PPSCI_E_UNSUPPORTED;
   }
   return PPSCI_OK;
@@ -449,7 +471,8 @@ extern "C" int ppsci_pirate_act_fwd(int mode, int act, int H, int64_t N, int64_t
                                     float* out, void* stream) {
   int rc = act_check(mode, act, H, N, NP, n1, n2);
   if (rc != PPSCI_OK) return rc;
-  if (!z || !bias || !out || (mode == PPSCI_PIRATE_GATE && (!U || !V)) || (mode == PPSCI_PIRATE_RES && (!x || !alpha))) {
+  if (!z || !bias || !out || (mode == PPSCI_PIRATE_GATE && (!U || !V)) || (mode == PPSCI_PIRATE_RES && (!x || !alpha)) ||
+      (act == PPSCI_ACT_SWISH && !alpha)) {
     ppsci_set_error("pirate_act_fwd: null argument");
     return PPSCI_E_INVALID;
   }
@@ -471,7 +494,8 @@ extern "C" int ppsci_pirate_act_bwd(int mode, int act, int H, int64_t N, int64_t
   int rc = act_check(mode, act, H, N, NP, n1, n2);
   if (rc != PPSCI_OK) return rc;
   if (!z || !bias || !obar || !zbar || !partials_b || (mode == PPSCI_PIRATE_GATE && (!U || !V || !Ubar || !Vbar)) ||
-      (mode == PPSCI_PIRATE_RES && (!x || !alpha || !xbar || !partials_alpha))) {
+      (mode == PPSCI_PIRATE_RES && (!x || !alpha || !xbar || !partials_alpha)) ||
+      (act == PPSCI_ACT_SWISH && (!alpha || !partials_alpha))) {
     ppsci_set_error("pirate_act_bwd: null argument");
     return PPSCI_E_INVALID;
   }
@@ -511,5 +535,249 @@ extern "C" int ppsci_pirate_out_bwd(int S, int m, int64_t N, int64_t NP, const f
   PPSCI_LAUNCH(pirate_out_bwd_kernel, PrOutArgs, (int)((total + PR_BLOCK - 1) / PR_BLOCK), PR_BLOCK, 0, stream, a);
   int e = PPSCI_LAST_LAUNCH_ERROR();
   if (e != 0) { ppsci_set_error("pirate_out_bwd: launch failed (%d)", e); return PPSCI_E_LAUNCH; }
+  return PPSCI_OK;
+}
+
+// ------------------------------------------------------------------------------------------ DeepONet head
+// ppsci.arch.DeepONet / HEDeepONets / ChipDeepONets (deeponet.py:129-154, he_deeponets.py:151-197,
+// chip_deeponets.py:186-214): with F = p * n_out trunk features, A = act(Z + trunk bias) on the trunk's Taylor streams
+// and B_j = (branch j output + its bias) (value only: the branch nets do not depend on the trunk inputs),
+//   G_o = sum_{k < p} prod_j B_j[o p + k] * A[o p + k] + b[o],  every stream of G_o the same sum over A's streams.
+struct OnetArgs {
+  const float* Z;                    // [S][F][NP] trunk last_fc output without its bias
+  const float* tbias;                // [F]
+  const float* B[PPSCI_ONET_MAX_J];  // [F][NP] branch last_fc outputs without their biases
+  const float* bb[PPSCI_ONET_MAX_J]; // [F]
+  const float* beta;                 // swish
+  const float* b;                    // [n_out] (nullptr: use_bias = False)
+  float* U;                          // fwd: [n_out * S][N]
+  const float* Ubar;                 // bwd
+  float* Zbar;                       // [S][F][NP]
+  float* Bbar[PPSCI_ONET_MAX_J];     // [F][NP]
+  float* p_tb;                       // [chunks][F]
+  float* p_bb;                       // [J][chunks][F]
+  float* p_beta;                     // [F * chunks]
+  float* p_b;                        // [chunks][n_out]
+  int J, p, n_out, n1, n2, act;
+  long long N, NP;
+};
+
+// the streams of a = act(z) for feature f at point i (Faa di Bruno, order 2)
+__device__ __forceinline__ void onet_act_streams(const OnetArgs& a, int f, long long i, float& s0, float (&ap)[PPSCI_MAX_DIRS],
+                                                 float (&app)[PPSCI_MAX_DIRS]) {
+  const long long plane = (long long)a.p * a.n_out * a.NP, e = (long long)f * a.NP + i;
+  float d1, d2, d3, sp, d1p, d2p;
+  pr_act_p(a.act, a.Z[e] + a.tbias[f], a.beta, s0, d1, d2, d3, sp, d1p, d2p);
+  for (int q = 0; q < a.n1; ++q) {
+    const float zp = a.Z[(1 + q) * plane + e];
+    ap[q] = d1 * zp;
+    app[q] = q < a.n2 ? d2 * zp * zp + d1 * a.Z[(1 + a.n1 + q) * plane + e] : 0.f;
+  }
+}
+
+// one thread per point; loops over the F features, every access contiguous along the points
+__global__ void __launch_bounds__(PR_BLOCK) onet_head_fwd_kernel(OnetArgs a) {
+  const long long i = (long long)blockIdx.x * PR_BLOCK + threadIdx.x;
+  if (i >= a.N) return;
+  const int n1 = a.n1, n2 = a.n2, S = 1 + n1 + n2;
+  for (int o = 0; o < a.n_out; ++o) {
+    float g0 = 0.f, g1[PPSCI_MAX_DIRS] = {0, 0, 0, 0}, g2[PPSCI_MAX_DIRS] = {0, 0, 0, 0};
+    for (int k = 0; k < a.p; ++k) {
+      const int f = o * a.p + k;
+      float w = a.B[0][(long long)f * a.NP + i] + a.bb[0][f];
+      for (int j = 1; j < a.J; ++j) w *= a.B[j][(long long)f * a.NP + i] + a.bb[j][f];
+      float s0, ap[PPSCI_MAX_DIRS], app[PPSCI_MAX_DIRS];
+      onet_act_streams(a, f, i, s0, ap, app);
+      g0 += w * s0;
+      for (int q = 0; q < n1; ++q) { g1[q] += w * ap[q]; g2[q] += w * app[q]; }
+    }
+    float* u = a.U + (long long)o * S * a.N + i;
+    u[0] = g0 + (a.b ? a.b[o] : 0.f);
+    for (int q = 0; q < n1; ++q) u[(1 + q) * a.N] = g1[q];
+    for (int q = 0; q < n2; ++q) u[(1 + n1 + q) * a.N] = g2[q];
+  }
+}
+
+// fixed-shape tree sums of NV values over the workgroup (one barrier sequence for all of them); valid in thread 0
+template <int NV>
+__device__ __forceinline__ void onet_block_sums(float (&v)[NV], float (*red)[PR_BLOCK]) {
+  __syncthreads();
+  for (int c = 0; c < NV; ++c) red[c][threadIdx.x] = v[c];
+  __syncthreads();
+  for (int w = PR_BLOCK / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int c = 0; c < NV; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + w];
+    __syncthreads();
+  }
+  for (int c = 0; c < NV; ++c) v[c] = red[c][0];
+}
+
+// one thread per (feature, point), a workgroup = one feature x PR_BLOCK points (same grid as pirate_act_bwd):
+// Abar_s = w Ubar_s, Zbar = Faa di Bruno reverse of act, Bbar_j = (sum_s A_s Ubar_s) prod_{j' != j} B_j';
+// per-workgroup sums of zbar_0 (trunk bias), Bbar_j (branch biases), the beta adjoint and Ubar_0 (b)
+template <int J>
+__global__ void __launch_bounds__(PR_BLOCK) onet_head_bwd_kernel(OnetArgs a) {
+  __shared__ float red[J + 3][PR_BLOCK];
+  const int nch = (int)((a.NP + PR_BLOCK - 1) / PR_BLOCK);
+  const int f = blockIdx.x / nch, ch = blockIdx.x % nch, o = f / a.p, F = a.p * a.n_out;
+  const long long i = (long long)ch * PR_BLOCK + threadIdx.x;
+  const int n1 = a.n1, n2 = a.n2, S = 1 + n1 + n2;
+  const long long plane = (long long)F * a.NP, e = (long long)f * a.NP + i;
+  float sums[J + 3];  // zbar_0, Bbar_0..J-1, beta, Ubar_0
+  for (int c = 0; c < J + 3; ++c) sums[c] = 0.f;
+  if (i < a.NP && i >= a.N) {
+    for (int s = 0; s < S; ++s) a.Zbar[s * plane + e] = 0.f;
+    for (int j = 0; j < J; ++j) a.Bbar[j][e] = 0.f;
+  } else if (i < a.N) {
+    float Bv[J];
+    for (int j = 0; j < J; ++j) Bv[j] = a.B[j][e] + a.bb[j][f];
+    float w = Bv[0];
+    for (int j = 1; j < J; ++j) w *= Bv[j];
+    float d1, d2, d3, s0, sp, d1p, d2p;
+    pr_act_p(a.act, a.Z[e] + a.tbias[f], a.beta, s0, d1, d2, d3, sp, d1p, d2p);
+    const float* ub = a.Ubar + (long long)o * S * a.N + i;
+    const float ub0 = ub[0];
+    float zp[PPSCI_MAX_DIRS], zpp[PPSCI_MAX_DIRS];
+    float G = s0 * ub0, zb0 = d1 * w * ub0, gbeta = sp * w * ub0;
+    for (int q = 0; q < n1; ++q) {
+      zp[q] = a.Z[(1 + q) * plane + e];
+      zpp[q] = q < n2 ? a.Z[(1 + n1 + q) * plane + e] : 0.f;
+      const float ub1 = ub[(1 + q) * a.N], ab1 = w * ub1;
+      G += d1 * zp[q] * ub1;
+      float z1b = d1 * ab1;
+      zb0 += d2 * zp[q] * ab1;
+      gbeta += d1p * zp[q] * ab1;
+      if (q < n2) {
+        const float ub2 = ub[(1 + n1 + q) * a.N], ab2 = w * ub2;
+        G += (d2 * zp[q] * zp[q] + d1 * zpp[q]) * ub2;
+        z1b += 2.f * d2 * zp[q] * ab2;
+        zb0 += (d3 * zp[q] * zp[q] + d2 * zpp[q]) * ab2;
+        gbeta += (d2p * zp[q] * zp[q] + d1p * zpp[q]) * ab2;
+        a.Zbar[(1 + n1 + q) * plane + e] = d1 * ab2;
+      }
+      a.Zbar[(1 + q) * plane + e] = z1b;
+    }
+    a.Zbar[e] = zb0;
+    for (int j = 0; j < J; ++j) {
+      float r = G;
+      for (int j2 = 0; j2 < J; ++j2)
+        if (j2 != j) r *= Bv[j2];
+      a.Bbar[j][e] = r;
+      sums[1 + j] = r;
+    }
+    sums[0] = zb0;
+    sums[J + 1] = gbeta;
+    sums[J + 2] = ub0;
+  }
+  onet_block_sums<J + 3>(sums, red);
+  if (threadIdx.x == 0) {
+    a.p_tb[(long long)ch * F + f] = sums[0];
+    for (int j = 0; j < J; ++j) a.p_bb[((long long)j * nch + ch) * F + f] = sums[1 + j];
+    if (a.p_beta) a.p_beta[blockIdx.x] = sums[J + 1];
+    if (a.p_b && f % a.p == 0) a.p_b[(long long)ch * a.n_out + o] = sums[J + 2];
+  }
+}
+
+// branch key [N][m] (row-major, as the dataset holds it) -> planar [m][NP] with zero padding
+struct OnetPackArgs {
+  const float* src;
+  float* dst;
+  int m;
+  long long N, NP;
+};
+
+__global__ void __launch_bounds__(PR_BLOCK) onet_pack_kernel(OnetPackArgs a) {
+  const long long t = (long long)blockIdx.x * PR_BLOCK + threadIdx.x;
+  if (t >= (long long)a.m * a.NP) return;
+  const long long i = t % a.NP;
+  const int c = (int)(t / a.NP);
+  a.dst[t] = i < a.N ? a.src[i * a.m + c] : 0.f;
+}
+
+static int onet_check(const ppsci_onet_head_desc* d, const char* who) {
+  if (!d || d->J < 1 || d->J > PPSCI_ONET_MAX_J || d->p < 1 || d->n_out < 1 || d->n_out > PPSCI_MAX_OUT || d->n1 < 0 ||
+      d->n1 > PPSCI_MAX_DIRS || d->n2 < 0 || d->n2 > d->n1 || d->N < 1 || d->NP < d->N || (d->NP & 15)) {
+    ppsci_set_error("%s: invalid descriptor (J in 1..%d, p >= 1, n_out in 1..%d, n2 <= n1 <= %d, NP >= N, NP %% 16 == 0)",
+                    who, PPSCI_ONET_MAX_J, PPSCI_MAX_OUT, PPSCI_MAX_DIRS);
+    return PPSCI_E_INVALID;
+  }
+  if (d->act != PPSCI_ACT_TANH && d->act != PPSCI_ACT_SILU && d->act != PPSCI_ACT_SIGMOID && d->act != PPSCI_ACT_COS &&
+      d->act != PPSCI_ACT_GELU && d->act != PPSCI_ACT_SIN && d->act != PPSCI_ACT_SWISH) {
+    ppsci_set_error("%s: activation %d has no head kernel (tanh, silu, sigmoid, sin, cos, gelu, swish)", who, d->act);
+    return PPSCI_E_INVALID;
+  }
+  return PPSCI_OK;
+}
+
+static void onet_fill(OnetArgs& a, const ppsci_onet_head_desc* d, const float* Z, const float* tbias, const float* const* B,
+                      const float* const* bb, const float* beta, const float* b) {
+  memset(&a, 0, sizeof(a));
+  a.Z = Z; a.tbias = tbias; a.beta = beta; a.b = b;
+  for (int j = 0; j < d->J; ++j) { a.B[j] = B[j]; a.bb[j] = bb[j]; }
+  a.J = d->J; a.p = d->p; a.n_out = d->n_out; a.n1 = d->n1; a.n2 = d->n2; a.act = d->act; a.N = d->N; a.NP = d->NP;
+}
+
+static bool onet_ptrs_ok(const ppsci_onet_head_desc* d, const float* const* B, const float* const* bb, const float* beta) {
+  if (!B || !bb || (d->act == PPSCI_ACT_SWISH && !beta)) return false;
+  for (int j = 0; j < d->J; ++j)
+    if (!B[j] || !bb[j]) return false;
+  return true;
+}
+
+extern "C" int64_t ppsci_onet_head_chunks(int64_t NP) { return (NP + PR_BLOCK - 1) / PR_BLOCK; }
+
+extern "C" int ppsci_onet_pack(int m, int64_t N, int64_t NP, const float* src, float* dst, void* stream) {
+  if (m < 1 || N < 1 || NP < N || (NP & 15) || !src || !dst) {
+    ppsci_set_error("onet_pack: invalid argument (m >= 1, NP >= N, NP %% 16 == 0, non-null pointers)");
+    return PPSCI_E_INVALID;
+  }
+  const long long total = (long long)m * NP;
+  OnetPackArgs a{src, dst, m, (long long)N, (long long)NP};
+  PPSCI_LAUNCH(onet_pack_kernel, OnetPackArgs, (int)((total + PR_BLOCK - 1) / PR_BLOCK), PR_BLOCK, 0, stream, a);
+  int e = PPSCI_LAST_LAUNCH_ERROR();
+  if (e != 0) { ppsci_set_error("onet_pack: launch failed (%d)", e); return PPSCI_E_LAUNCH; }
+  return PPSCI_OK;
+}
+
+extern "C" int ppsci_onet_head_fwd(const ppsci_onet_head_desc* d, const float* Z, const float* tbias, const float* const* B_host,
+                                   const float* const* bbias_host, const float* beta, const float* b, float* U, void* stream) {
+  if (onet_check(d, "onet_head_fwd") != PPSCI_OK) return PPSCI_E_INVALID;
+  if (!Z || !tbias || !U || !onet_ptrs_ok(d, B_host, bbias_host, beta)) {
+    ppsci_set_error("onet_head_fwd: null argument");
+    return PPSCI_E_INVALID;
+  }
+  OnetArgs a;
+  onet_fill(a, d, Z, tbias, B_host, bbias_host, beta, b);
+  a.U = U;
+  PPSCI_LAUNCH(onet_head_fwd_kernel, OnetArgs, (int)((d->N + PR_BLOCK - 1) / PR_BLOCK), PR_BLOCK, 0, stream, a);
+  int e = PPSCI_LAST_LAUNCH_ERROR();
+  if (e != 0) { ppsci_set_error("onet_head_fwd: launch failed (%d)", e); return PPSCI_E_LAUNCH; }
+  return PPSCI_OK;
+}
+
+extern "C" int ppsci_onet_head_bwd(const ppsci_onet_head_desc* d, const float* Z, const float* tbias, const float* const* B_host,
+                                   const float* const* bbias_host, const float* beta, const float* Ubar, float* Zbar,
+                                   float* const* Bbar_host, float* partials_tbias, float* partials_bbias,
+                                   float* partials_beta, float* partials_b, void* stream) {
+  if (onet_check(d, "onet_head_bwd") != PPSCI_OK) return PPSCI_E_INVALID;
+  if (!Z || !tbias || !Ubar || !Zbar || !Bbar_host || !partials_tbias || !partials_bbias || !onet_ptrs_ok(d, B_host, bbias_host, beta) ||
+      (d->act == PPSCI_ACT_SWISH && !partials_beta)) {
+    ppsci_set_error("onet_head_bwd: null argument");
+    return PPSCI_E_INVALID;
+  }
+  for (int j = 0; j < d->J; ++j)
+    if (!Bbar_host[j]) { ppsci_set_error("onet_head_bwd: null argument"); return PPSCI_E_INVALID; }
+  OnetArgs a;
+  onet_fill(a, d, Z, tbias, B_host, bbias_host, beta, nullptr);
+  a.Ubar = Ubar; a.Zbar = Zbar; a.p_tb = partials_tbias; a.p_bb = partials_bbias;
+  a.p_beta = d->act == PPSCI_ACT_SWISH ? partials_beta : nullptr;
+  a.p_b = partials_b;
+  for (int j = 0; j < d->J; ++j) a.Bbar[j] = Bbar_host[j];
+  const long long grid = (long long)d->p * d->n_out * ppsci_onet_head_chunks(d->NP);
+  if (d->J == 1) PPSCI_LAUNCH(onet_head_bwd_kernel<1>, OnetArgs, (int)grid, PR_BLOCK, 0, stream, a);
+  else if (d->J == 2) PPSCI_LAUNCH(onet_head_bwd_kernel<2>, OnetArgs, (int)grid, PR_BLOCK, 0, stream, a);
+  else PPSCI_LAUNCH(onet_head_bwd_kernel<3>, OnetArgs, (int)grid, PR_BLOCK, 0, stream, a);
+  int e = PPSCI_LAST_LAUNCH_ERROR();
+  if (e != 0) { ppsci_set_error("onet_head_bwd: launch failed (%d)", e); return PPSCI_E_LAUNCH; }
   return PPSCI_OK;
 }

@@ -523,6 +523,9 @@ def net_raw_vars(model) -> Tuple[str, ...]:
     """The data-dict variables a network's outputs depend on: its input keys, or -- with a registered input
     transform -- the raw variables its input features are built from."""
     feats = getattr(model, "_traced_features", None)
+    branch = getattr(model, "branch_keys", None)
+    if branch:  # operator nets (arch/deeponet.py): the branch keys are [N, m] tensors of the executor, not stream variables
+        return tuple(k for k in model.input_keys if k not in branch)
     if not feats:
         return tuple(model.input_keys)
     names: List[str] = []
@@ -568,6 +571,9 @@ def diff(e: Sym, var: str) -> Sym:
         raise NotImplementedError(f"derivative of the batch reduction {e!r} w.r.t. the per-point variable {var!r}: differentiate "
                                   "first, reduce afterwards")
     if k == "net":
+        if var in (getattr(e.model, "branch_keys", None) or ()):
+            raise NotImplementedError(f"derivative of {type(e.model).__name__} output {e!r} w.r.t. its branch key {var!r}: "
+                                      "derivatives run along the trunk keys only")
         if var not in net_raw_vars(e.model):
             return Sym.const(0.0)
         if len(e.dirs) >= 4:
@@ -711,6 +717,12 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
     models = {id(n.model): n.model for n in nodes if n.kind == "net"}  # ModelList members: in order of appearance
     model_list = list(models.values())
     model = model_list[0] if model_list else None
+    for mm in model_list:  # operator nets: a multi-column branch key is no per-point variable of the residual program
+        cols = getattr(mm, "branch_cols", None) or {}
+        for n in nodes:
+            if n.kind in ("in", "aux") and cols.get(n.name, 1) != 1:
+                raise NotImplementedError(f"expression reads the {cols[n.name]}-column branch key {n.name!r} of "
+                                          f"{type(mm).__name__}: only one-column keys are per-point values")
 
     # ---- derivative set -> stream specification
     # order[d] = highest pure derivative order needed along direction d (a variable, (a, b) = a + b, (a, b, -1) = a - b)
@@ -803,7 +815,7 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
             pre_nets[id(mm)] = blocks
             spec = hp.StreamSpec([[0.0] * len(mm.input_keys) for _ in range(n1p)], n2p, n3p, n4p)
         else:
-            idx = [in_keys.index(k) for k in mm.input_keys]
+            idx = [in_keys.index(k) for k in net_raw_vars(mm)]
             spec = hp.StreamSpec([[v[j] for j in idx] for v in dirs_vec], n2p, n3p, n4p)
         nets.append((mm, spec, rows, idx))
         row0[id(mm)] = rows
