@@ -812,6 +812,82 @@ int ppsci_modmlp_bwd_batch_parts(const ppsci_modmlp_desc* d, const ppsci_spinn_g
                                  const float* const* x, const float* scratch, const float* const* stash,
                                  float* const* grad_partials, int64_t partial_stride, void* stream);
 
+/* ---- ppsci.arch.LNO, the Laplace neural operator (csrc/lno.inc, included by csrc/uno.hip) ---------------------------
+ * Grid n[0] x n[1] x n[2] (N points), C channels, modes m[0] x m[1] x m[2] (M coefficients), pair = i * C + o.  Complex planes
+ * are [plane][2][N] (real plane, imaginary plane), coefficient tensors [..][M][2]; the residues are the model's two real
+ * parameter tensors [C*C][M].  Every kernel sums in a fixed order: results are bitwise repeatable. */
+/* 1 when the planes and intermediates of every LNO kernel fit LDS at this shape. */
+int ppsci_lno_supported(int n1, int n2, int n3, int m1, int m2, int m3);
+/* lno.py:142-152, :169-182: A_d[pair][m][p] = 1 / (i omega_d[p] - mu_d[pair][m]), E_d[pair][m][s] = exp(mu_d[pair][m] t_d[s]);
+ * all arguments are host arrays of three entries (device pointers); A_d, E_d: [C*C][m_d][n_d][2]. */
+int ppsci_lno_tables(int C, const int* n, const int* m, const float* const* mu_re, const float* const* mu_im,
+                     const float* const* omega, const float* const* t, float* const* A, float* const* E, void* stream);
+/* lno.py:161, :164-167: dense DFT along the three axes of each plane (any sizes; twiddles tw [n1 + n2 + n3][2] =
+ * (cos, sin)(2 pi k / n_d) from the host).  sign -1: e^{-i..} (fftn), +1: its adjoint; with out_scale = 1/N the inverse.
+ * in_mode 0: real planes [planes][N]; 1: complex planes; 2: the channel mix of lno.py:154 on load, plane (b, cp) =
+ * mix_scale * sum_c2 in[b, c2] * (conj_h: conj) H[cp * pair_cp + c2 * pair_c2] (+ add[b, cp], complex planes or NULL).
+ * out_real: the real part as [planes][N] (accumulate: added to what is there), else complex planes.
+ * zero_dc: where the frequency-0 coefficient is zero by construction (the spectrum of an instance-normalised plane; a
+ * gradient that an instance norm's reverse takes the mean out of) it is SET to zero instead of carrying fp32 rounding noise
+ * into a transfer function whose gain there is 1 / |mu_1 mu_2 mu_3|: 1 = element 0 of the input spectrum, 2 = of the output
+ * spectrum, 0 = off. */
+int ppsci_lno_dft3(int planes, int n1, int n2, int n3, int in_mode, const float* in, int C, const float* H, int pair_cp,
+                   int pair_c2, int conj_h, float mix_scale, const float* add, const float* tw, int sign, int out_real,
+                   int accumulate, float out_scale, int zero_dc, float* out, void* stream);
+typedef struct ppsci_lno_tri_desc {
+  int32_t n[3], m[3];
+  int32_t nb, ncp, nc2;           /* planes (b, cp), b < nb, cp < ncp; per plane a loop over c2 < nc2 */
+  int32_t C;                      /* the tables hold C * C pairs */
+  int32_t pair_cp, pair_c2;       /* pair = cp * pair_cp + c2 * pair_c2 */
+  int32_t conj_t;                 /* use conj(T_d) */
+  int32_t coef_b, coef_cp, coef_c2; /* coefficient block of (b, cp, c2): coef + (b*coef_b + cp*coef_cp + c2*coef_c2) * M * 2 */
+  int32_t mult_conj;
+  float gscale;                   /* c[mnk] = gscale * coef[..][mnk] * (mult_conj: conj) mult[pair][mnk]; a NULL factor is 1 */
+} ppsci_lno_tri_desc;
+/* The einsum eq2 of lno.py:115-126 without the residues: G[(plane, c2)][mnk] = sum_pqr X[pqr] T_1[m,p] T_2[n,q] T_3[k,r] (G may
+ * be NULL).  With mu_re != NULL also the reverse chain for the cotangent c[mnk] of G: dL/dmu_d of this (b, pair), written to
+ * row (row0 + b) of mu_re[d] / mu_im[d] [rows][C*C*m_d]; kind 0: T = A tables (dT/dmu = T^2), 1: T = E tables (dT/dmu = t T,
+ * tg = the three grids). */
+int ppsci_lno_analysis(const ppsci_lno_tri_desc* d, const float* X, int x_real, const float* const* T, float* G,
+                       const float* coef, const float* mult_re, const float* mult_im, int kind, const float* const* tg,
+                       float* const* mu_re, float* const* mu_im, int row0, void* stream);
+/* The einsums eq1 (H from the residues) and eq_x2 of lno.py:103-134, :184: out[plane][pqr] = out_scale * sum_c2 sum_mnk c[mnk]
+ * T_1[m,p] T_2[n,q] T_3[k,r]; out_real: the real part as [planes][N] (accumulate: added), else complex planes. */
+int ppsci_lno_synthesis(const ppsci_lno_tri_desc* d, const float* const* T, const float* coef, const float* mult_re,
+                        const float* mult_im, int out_real, int accumulate, float out_scale, float* out, void* stream);
+/* dst[b, o] = scale * sum_j src[b, j, o] * mult[j, o] on coefficient tensors (the residue product and channel sum of eq2). */
+int ppsci_lno_channel_sum(int B, int C, int M, const float* src, const float* mult_re, const float* mult_im, float scale,
+                          float* dst, void* stream);
+/* d rho[i, o] = Gp[i, o] - sum_b conj(Gam[b, i, o]) gbar[b, o], written to the two real gradient tensors. */
+int ppsci_lno_rho_grad(int B, int C, int M, const float* Gam, const float* gbar, const float* Gp, float* g_re, float* g_im,
+                       void* stream);
+/* Hbar[i, o] = scale * sum_b conj(alpha[b, i]) ghat[b, o] on complex planes (the reverse of the channel mix w.r.t. H). */
+int ppsci_lno_hbar(int B, int C, int N, const float* alpha, const float* ghat, float scale, float* hbar, void* stream);
+/* nn.InstanceNorm3D without affine (lno.py:244-248, :288) on [planes][N]: two-pass statistics, biased variance;
+ * stats [planes][2] = mean, 1/sqrt(var + eps).  Reverse from the normalised output y; `add` (or NULL) is added to dL/dx. */
+int ppsci_lno_inorm_fwd(int planes, int N, float eps, const float* x, float* y, float* stats, void* stream);
+int ppsci_lno_inorm_bwd(int planes, int N, const float* y, const float* gy, const float* stats, const float* add, float* gx,
+                        void* stream);
+/* Rows of the partial-sum matrices of the two per-point reverse kernels below. */
+int64_t ppsci_lno_point_rows(int64_t points);
+/* fc0 (lno.py:281-285): x [B][N][fd] channel-last (+ the three linspace(0, 1, n_d) channels of get_grid with use_grid), W
+ * [fd (+3)][C], h [B][C][N].  Reverse: gx [B][N][fd] (or NULL), partial rows [ppsci_lno_point_rows(B*N)][(fd (+3)) * C + C]. */
+int ppsci_lno_lift_fwd(int B, int n1, int n2, int n3, int fd, int use_grid, int C, const float* x, const float* W,
+                       const float* bias, float* h, void* stream);
+int ppsci_lno_lift_bwd(int B, int n1, int n2, int n3, int fd, int use_grid, int C, const float* x, const float* W,
+                       const float* gh, float* gx, float* partials, void* stream);
+/* lno.py:292-299: y = fc2(act(fc1(x1 + conv(h)))) per grid point; Wc [C][C] (out, in), W1 [C][Hd], W2 [Hd]; act: PPSCI_ACT_*
+ * without the parametrised ones (swish, stan).  Reverse: gx1 = dL/dx1, gh = the convolution's share of dL/dh, partial rows
+ * [ppsci_lno_point_rows(B*N)][C*C + C + C*Hd + Hd + Hd + 1] in the order conv.weight, conv.bias, fc1.weight, fc1.bias,
+ * fc2.weight, fc2.bias. */
+int ppsci_lno_head_supported(int C, int Hd);
+int ppsci_lno_head_fwd(int B, int N, int C, int Hd, int act, const float* x1, const float* h, const float* Wc,
+                       const float* bc, const float* W1, const float* b1, const float* W2, const float* b2, float* y,
+                       void* stream);
+int ppsci_lno_head_bwd(int B, int N, int C, int Hd, int act, const float* x1, const float* h, const float* Wc,
+                       const float* bc, const float* W1, const float* b1, const float* W2, const float* gy, float* gx1,
+                       float* gh, float* partials, void* stream);
+
 /* ---- data-parallel collectives on RCCL (csrc/comm.hip): the fused gradient all-reduce of solver/train.py:168-171 and
  * the evaluation gather of utils/misc.py, on the ONE flat gradient buffer -- so that a host without torch.distributed can
  * drive data parallelism through this library: ppsci_taylor_step_run_ex (no Adam) -> ppsci_allreduce_sum on `grad` ->

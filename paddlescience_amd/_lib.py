@@ -84,6 +84,12 @@ class OnetHeadDesc(C.Structure):  # ppsci_onet_head_desc
                 ("act", C.c_int32), ("N", C.c_int64), ("NP", C.c_int64)]
 
 
+class LnoTriDesc(C.Structure):  # ppsci_lno_tri_desc
+    _fields_ = ([("n", C.c_int32 * 3), ("m", C.c_int32 * 3)] + [(k, C.c_int32) for k in (
+        "nb", "ncp", "nc2", "C", "pair_cp", "pair_c2", "conj_t", "coef_b", "coef_cp", "coef_c2", "mult_conj")]
+        + [("gscale", C.c_float)])
+
+
 class Instr(C.Structure):
     _fields_ = [("op", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("c", C.c_float)]
 
@@ -272,6 +278,26 @@ _SYMBOLS = {
     "ppsci_onet_head_bwd": (C.c_int, [C.POINTER(OnetHeadDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
                             + [C.c_void_p] * 5),
+    "ppsci_lno_supported": (C.c_int, [C.c_int] * 6),
+    "ppsci_lno_tables": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_void_p)] * 6 + [C.c_void_p]),
+    "ppsci_lno_dft3": (C.c_int, [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "ppsci_lno_analysis": (C.c_int, [C.POINTER(LnoTriDesc), C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    "ppsci_lno_synthesis": (C.c_int, [C.POINTER(LnoTriDesc), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "ppsci_lno_channel_sum": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_void_p]),
+    "ppsci_lno_rho_grad": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 6),
+    "ppsci_lno_hbar": (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "ppsci_lno_inorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 4),
+    "ppsci_lno_inorm_bwd": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "ppsci_lno_point_rows": (C.c_int64, [C.c_int64]),
+    "ppsci_lno_lift_fwd": (C.c_int, [C.c_int] * 7 + [C.c_void_p] * 5),
+    "ppsci_lno_lift_bwd": (C.c_int, [C.c_int] * 7 + [C.c_void_p] * 6),
+    "ppsci_lno_head_supported": (C.c_int, [C.c_int, C.c_int]),
+    "ppsci_lno_head_fwd": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 10),
+    "ppsci_lno_head_bwd": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 12),
     "ppsci_spinn_grid_partial_rows": (C.c_int64, [C.POINTER(SpinnGridDesc)]),
     "ppsci_spinn_grid_fwd": (C.c_int, [C.POINTER(SpinnGridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

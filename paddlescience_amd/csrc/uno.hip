@@ -138,3 +138,6 @@ extern "C" int ppsci_resample2d(int n, int H, int W, int H2, int W2, const float
   }
   return PPSCI_OK;
 }
+
+// ---- the Laplace neural operator's kernels (a file of their own; this unit is their translation unit)
+#include "lno.inc"

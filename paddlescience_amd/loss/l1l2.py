@@ -76,6 +76,20 @@ class L2RelLoss(_PointLoss):
         loss = torch.linalg.norm((x - y).reshape(n, -1), dim=1) / torch.linalg.norm(y.reshape(n, -1), dim=1)
         return loss * w if w is not None else loss
 
+    def value_and_grad(self, y_net, label, key):
+        """Operator-learning path (operator_engine.OperatorConstraint), unweighted: the loss on a field of any rank and its
+        adjoint from the field-loss kernels (loss/field.py, mode REL on the values) -- per sample ||x - y||_2 / ||y||_2 over all
+        non-batch axes (l2.py:280-286: the field viewed as [B, 1, N, 1]), sum / mean over the batch, times the key weight."""
+        from . import field
+
+        plan = self.__dict__.setdefault("_field_plan", field.FieldLossPlan(field.VALUES, field.REL))
+        B = y_net.shape[0]
+        coef = self.key_weight(key) / (B if self.reduction == "mean" else 1.0)
+        x = y_net.contiguous().view(B, 1, -1, 1)
+        y = label.to(dtype=torch.float32).contiguous().view(B, 1, -1, 1)
+        loss, g = plan.value_and_grad(x, y, coef)
+        return {key: loss.reshape(())}, g.view(y_net.shape)
+
     def batch_weight(self, w):
         """The per-point weight column the epilogue multiplies by, such that its reduction equals the reference's
         reduction of the broadcast [N, N] product (see `_point`)."""

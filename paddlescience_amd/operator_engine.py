@@ -70,9 +70,10 @@ class OperatorConstraint:
         torch w.r.t. that one tensor (nothing of the network is on an autograd tape)."""
         m = self.model
         if m._input_transform is not None or m._output_transform is not None:
-            raise NotImplementedError("training an FNONet with registered input / output transforms")
+            raise NotImplementedError(f"training an {type(m).__name__} with registered input / output transforms")
         xs = [self.inp[k] for k in m.input_keys]
-        x = xs[0] if len(xs) == 1 else torch.cat(xs, dim=1)
+        # (the channel axis: 1 for the [B, C, H, W] fields of FNO / UNO / SFNO, -1 for LNO's channel-last fields)
+        x = xs[0] if len(xs) == 1 else torch.cat(xs, dim=getattr(m, "channel_axis", 1))
         key = m.output_keys[0]
         y = native.forward(x)
         raw = (not self.output_expr or (list(self.output_expr) == [key] and getattr(self.output_expr[key], "is_identity", False))
@@ -121,12 +122,12 @@ class OperatorEngine:
 
         self._step_graph = StepGraph(self.grad.is_cuda and os.environ.get("PPSCI_HIP_GRAPH", "1") != "0")
         # forward and backward on this framework's own kernels, no autograd graph of the network (fno_engine.py)
-        from . import fno_engine, uno_engine
+        from . import fno_engine, lno_engine, uno_engine
 
         why = fno_engine.supports(model)
-        if why is not None and uno_engine.supports(model) is not None:
+        if why is not None and uno_engine.supports(model) is not None and lno_engine.supports(model) is not None:
             raise NotImplementedError(f"operator engine: {why}")
-        self.native = model.native()  # fno_engine.FnoNative / uno_engine.UnoNative
+        self.native = model.native()  # fno_engine.FnoNative / uno_engine.UnoNative / lno_engine.LnoNative
 
     def _forward_backward_eager(self, constraints: List[OperatorConstraint]):
         if len(constraints) != 1:
