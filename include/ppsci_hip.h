@@ -692,6 +692,7 @@ void ppsci_set_modmlp_tile(int mode);
  * (csrc/field_loss.hip).  LpLoss / H1Loss of /root/reference/examples/neuraloperator/metric.py:69-412 (p = 2, d = 2;
  * central differences :36-55, wrapping around or one-sided at the ends under fix_x / fix_y) and MSELoss on fields
  * (ppsci/loss/mse.py:82-105), plus what autograd derives from them in the reference.  With e = x - y:
+ *   (sums [rows][2] are DOUBLES: the row sums, the terms and their total are carried in double and rounded once, at loss[0])
  *   _sums:    sums[2 r] = |e|^2 (+ |Dx e|^2 + |Dy e|^2, order 1),  sums[2 r + 1] = the same of y;  ihx / ihy = 1 / spacing
  *             (order 2: the p = 1 norms -- sums of |e| and |y|, no differences)
  *   _finish:  term(r) = sqrt(S_diff)/sqrt(S_y) (mode 0, rel) | sqrt(abs_const S_diff) (1, abs) | S_diff (2, squared) |
@@ -699,8 +700,8 @@ void ppsci_set_modmlp_tile(int mode);
  *             loss[0] = coef * sum_r term(r) (fixed order);  rowcoef[r] = coef * d term / d S_diff * 2 (may be NULL)
  *   _adjoint: gx = rowcoef[r] (e + Dx^T Dx e + Dy^T Dy e) = d loss / d x */
 int ppsci_field_loss_sums(int rows, int H, int W, int order, float ihx, float ihy, int fix_x, int fix_y, const float* x,
-                          const float* y, float* sums, void* stream);
-int ppsci_field_loss_finish(int rows, int mode, float abs_const, float coef, const float* sums, float* loss, float* rowcoef,
+                          const float* y, double* sums, void* stream);
+int ppsci_field_loss_finish(int rows, int mode, float abs_const, float coef, const double* sums, float* loss, float* rowcoef,
                             void* stream);
 int ppsci_field_loss_adjoint(int rows, int H, int W, int order, float ihx, float ihy, int fix_x, int fix_y, const float* x,
                              const float* y, const float* rowcoef, float* gx, void* stream);
@@ -887,6 +888,74 @@ int ppsci_lno_head_fwd(int B, int N, int C, int Hd, int act, const float* x1, co
 int ppsci_lno_head_bwd(int B, int N, int C, int Hd, int act, const float* x1, const float* h, const float* Wc,
                        const float* bc, const float* W1, const float* b1, const float* W2, const float* gy, float* gx1,
                        float* gh, float* partials, void* stream);
+
+/* ---- ppsci.arch.FNO1d, the 1-D Fourier neural operator of Geo-FNO (csrc/fno1d.inc, included by csrc/uno.hip) ---------
+ * Activations [B][C][L] fp32, M kept modes; spectra are [B * C][2M] (re, im interleaved per mode).  Both transforms are GEMMs
+ * against tables built once per shape on the host (geofno_engine.tables): analysis Ta [L][2M] = (cos, -sin)(2 pi l m / L),
+ * synthesis Ts [2M][n] = c_m / n (cos, -sin)(2 pi l m / n) with the irfft conventions (no imaginary DC / Nyquist row, rows
+ * beyond n / 2 zero) folded in; the reverse pass uses their transposes with the same kernels.  Every kernel sums in a fixed
+ * order and none uses atomics: results are bitwise repeatable. */
+/* Rows of the partial-sum matrix of ppsci_fno1d_lift_bwd. */
+int64_t ppsci_fno1d_point_rows(int64_t points);
+/* geofno.py:170-173: fc0 on x [B][s][fin] (W [fin][C]), transposed to h [B][C][Lp] and zero on s <= l < Lp.  Reverse: gh
+ * [B][C][Lp] (its padded tail is ignored: the adjoint of the crop), gx [B][s][fin], partial rows
+ * [ppsci_fno1d_point_rows(B*s)][fin * C + C] (fc0.weight, fc0.bias). */
+int ppsci_fno1d_lift_fwd(int B, int s, int Lp, int fin, int C, const float* x, const float* W, const float* bias, float* h,
+                         void* stream);
+int ppsci_fno1d_lift_bwd(int B, int s, int Lp, int fin, int C, const float* x, const float* W, const float* gh, float* gx,
+                         float* partials, void* stream);
+/* geofno.py:71 (rfft on the kept modes) and the adjoint of :88-90: part[s][r][j] = sum over the s-th of S slices of k < K of
+ * x[r * ldx + k] T[k][j], r < R, j < N2 -- a tall-skinny GEMM split over K; the consumer (ppsci_fno1d_mix) adds the S slices
+ * in ascending order. */
+int ppsci_fno1d_analysis(int R, int K, int N2, int S, int64_t ldx, const float* x, const float* T, float* part, void* stream);
+/* geofno.py:48-66, :82-84: the complex channel mix per kept mode on the sum of the S analysis slices `part` [S][B*C][2M] (the
+ * sum is also written to `sum` [B*C][2M] unless NULL); wr / wi [C][C][M] (in, out, mode).  conj 0: out[b,o,m] = sum_i
+ * in[b,i,m] W[i,o,m]; conj 1: out[b,i,m] = sum_o in[b,o,m] conj(W[i,o,m]), its adjoint. */
+int ppsci_fno1d_mix(int B, int C, int M, int S, int conj, const float* part, float* sum, const float* wr, const float* wi,
+                    float* out, void* stream);
+/* dL/dW[i,o,m] = sum_b conj(X[b,i,m]) Ybar[b,o,m], written to the two real gradient tensors [C][C][M]. */
+int ppsci_fno1d_mix_wgrad(int B, int C, int M, const float* X, const float* Yb, float* gwr, float* gwi, void* stream);
+/* geofno.py:175-198 and :201-203, one GEMM per (sample, 64 columns) with K = K1 + K2:
+ *   acc[b][r][l] = sum_{k < K1} A1[b][r][k] T[k][l] + sum_{c < K2} A2[r * a2_rs + c * a2_cs] X2[b][c][l]    r < R, l < Lc
+ * (X2 is read as zero at l >= x2_len).  Epilogue, in this order, every pointer optional: + bias[r]; + linear interpolation
+ * (1 - ip_t[l]) ip_src[b][r][ip_i0[l]] + ip_t[l] ip_src[b][r][ip_i0[l] + 1], or its adjoint: + sum over j in
+ * [ia_first[max(l - 1, 0)], ia_first[l + 1]) of (ip_i0[j] == l ? 1 - ip_t[j] : ip_t[j]) ia_src[b][r][j] (ia_first[i] = the
+ * first j with ip_i0[j] >= i); store to v; times gelu'(dact_v[b][r][l]); act != 0: exact-erf GELU; store to out; hy[b][l] =
+ * sum_r hw2[r] value + hb2[0].  Columns Lc <= l < Lout of out are written as zeros.  Forward layer: A1 = Y, T = Ts, A2 = Wc,
+ * X2 = x; reverse: A1 = Xbar, T = Ta^T, A2 = Wc^T (strides), X2 = gv; head: R = fc1's outputs, A2 = fc1.weight^T. */
+typedef struct ppsci_fno1d_layer_desc {
+  const float* A1;       /* [B][R][K1], sample stride a1_bs */
+  const float* T;        /* [K1][ldt] */
+  const float* A2;
+  const float* X2;       /* [B][K2][x2_ld], sample stride x2_bs */
+  const float* bias;
+  const float* ip_src;   /* [B][R][ip_ld], sample stride ip_bs */
+  const int32_t* ip_i0;
+  const float* ip_t;
+  const float* ia_src;   /* [B][R][ia_ld], sample stride ia_bs */
+  const int32_t* ia_first;
+  const float* dact_v;   /* [B][R][dv_ld], sample stride dv_bs */
+  float* v;              /* v and out: [B][R][o_ld], sample stride o_bs */
+  float* out;
+  const float* hw2;
+  const float* hb2;
+  float* hy;             /* [B][Lout] */
+  int64_t a1_bs, a2_rs, a2_cs, x2_bs, ip_bs, ia_bs, dv_bs, o_bs;
+  int32_t ldt, x2_ld, x2_len, ip_ld, ia_ld, dv_ld, o_ld;
+  int32_t act, B, R, K1, K2, Lc, Lout;
+} ppsci_fno1d_layer_desc;
+/* 1 when R rows with K = K1 + K2 fit the layer kernel (R <= 128, both A operands in LDS). */
+int ppsci_fno1d_layer_supported(int R, int K1, int K2);
+int ppsci_fno1d_layer(const ppsci_fno1d_layer_desc* d, void* stream);
+/* Weight and bias gradient of a 1x1 convolution / per-point linear layer as partial rows per (sample, chunk of `chunk` points,
+ * a multiple of 16): partials[b * nchunks + ch][r1 * R2 + r2] = sum_{l in chunk} P[b][r1][l] Q[b][r2][l], followed by the row
+ * sums of P (bias_of 1) or of Q (bias_of 2) or nothing (0); nchunks = ceil(len / chunk); R1, R2 <= 128. */
+int ppsci_fno1d_wgrad(int B, int R1, int R2, int len, int chunk, int bias_of, const float* P, int64_t p_bs, int ldp,
+                      const float* Q, int64_t q_bs, int ldq, float* partials, void* stream);
+/* First stage of the head's reverse (geofno.py:201-203): gz[b][j][l] = gy[b][l] w2[j] gelu'(z[b][j][l]) and the partial rows
+ * [B * ceil(n / 256)][Hd + 1] of fc2.weight (sum_l gy gelu(z)) and fc2.bias (sum_l gy). */
+int ppsci_fno1d_head_pre(int B, int Hd, int n, const float* z, const float* gy, const float* w2, float* gz, float* partials,
+                         void* stream);
 
 /* ---- data-parallel collectives on RCCL (csrc/comm.hip): the fused gradient all-reduce of solver/train.py:168-171 and
  * the evaluation gather of utils/misc.py, on the ONE flat gradient buffer -- so that a host without torch.distributed can

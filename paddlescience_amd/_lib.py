@@ -84,6 +84,14 @@ class OnetHeadDesc(C.Structure):  # ppsci_onet_head_desc
                 ("act", C.c_int32), ("N", C.c_int64), ("NP", C.c_int64)]
 
 
+class Fno1dLayerDesc(C.Structure):  # ppsci_fno1d_layer_desc
+    _fields_ = ([(k, C.c_void_p) for k in ("A1", "T", "A2", "X2", "bias", "ip_src", "ip_i0", "ip_t", "ia_src", "ia_first", "dact_v",
+                                           "v", "out", "hw2", "hb2", "hy")]
+                + [(k, C.c_int64) for k in ("a1_bs", "a2_rs", "a2_cs", "x2_bs", "ip_bs", "ia_bs", "dv_bs", "o_bs")]
+                + [(k, C.c_int32) for k in ("ldt", "x2_ld", "x2_len", "ip_ld", "ia_ld", "dv_ld", "o_ld", "act", "B", "R", "K1", "K2",
+                                            "Lc", "Lout")])
+
+
 class LnoTriDesc(C.Structure):  # ppsci_lno_tri_desc
     _fields_ = ([("n", C.c_int32 * 3), ("m", C.c_int32 * 3)] + [(k, C.c_int32) for k in (
         "nb", "ncp", "nc2", "C", "pair_cp", "pair_c2", "conj_t", "coef_b", "coef_cp", "coef_c2", "mult_conj")]
@@ -298,6 +306,16 @@ _SYMBOLS = {
     "ppsci_lno_head_supported": (C.c_int, [C.c_int, C.c_int]),
     "ppsci_lno_head_fwd": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 10),
     "ppsci_lno_head_bwd": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 12),
+    "ppsci_fno1d_point_rows": (C.c_int64, [C.c_int64]),
+    "ppsci_fno1d_lift_fwd": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5),
+    "ppsci_fno1d_lift_bwd": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 6),
+    "ppsci_fno1d_analysis": (C.c_int, [C.c_int] * 4 + [C.c_int64] + [C.c_void_p] * 4),
+    "ppsci_fno1d_mix": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 6),
+    "ppsci_fno1d_mix_wgrad": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 5),
+    "ppsci_fno1d_layer_supported": (C.c_int, [C.c_int] * 3),
+    "ppsci_fno1d_layer": (C.c_int, [C.POINTER(Fno1dLayerDesc), C.c_void_p]),
+    "ppsci_fno1d_wgrad": (C.c_int, [C.c_int] * 6 + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "ppsci_fno1d_head_pre": (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 6),
     "ppsci_spinn_grid_partial_rows": (C.c_int64, [C.POINTER(SpinnGridDesc)]),
     "ppsci_spinn_grid_fwd": (C.c_int, [C.POINTER(SpinnGridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -36,51 +36,57 @@ __device__ __forceinline__ float fl_dapply(const float* v, long long stride, int
 struct FieldArgs {
   const float* x;
   const float* y;
-  float* sums;           // [rows][2]: S_diff, S_y
+  double* sums;          // [rows][2]: S_diff, S_y
   const float* rowcoef;  // [rows] (adjoint)
   float* gx;             // [rows][H][W] (adjoint)
   int rows, H, W, order, fix_x, fix_y;
   float ihx, ihy;
 };
 
+// The row sums, the rows' terms and their total are carried in double and rounded ONCE, at the store of the loss: a relative
+// loss is a sum of O(1) terms, and fp32 sums of fp32 terms left it up to one unit in the last place from the float32 nearest
+// to the exact value of the same fields -- more than a float32 training run's own deviation from a float64 one per step.
 // one workgroup per row; fixed-order block reduction (deterministic)
 __global__ void __launch_bounds__(256) field_sums_kernel(FieldArgs a) {
-  __shared__ float red[2][4];
+  __shared__ double red[2][256];
   const int r = blockIdx.x;
   const long long P = (long long)a.H * a.W;
   const float* x = a.x + r * P;
   const float* y = a.y + r * P;
-  float sd = 0.f, sy = 0.f;
+  double sd = 0., sy = 0.;
   for (int p = threadIdx.x; p < (int)P; p += 256) {
     const float yv = y[p], e = x[p] - yv;
     if (a.order == 2) {  // p = 1: sums of magnitudes
-      sd += fabsf(e);
-      sy += fabsf(yv);
+      sd += (double)fabsf(e);
+      sy += (double)fabsf(yv);
       continue;
     }
-    sd += e * e;
-    sy += yv * yv;
+    sd += (double)e * (double)e;
+    sy += (double)yv * (double)yv;
     if (a.order == 1) {
       const int i = p / a.W, j = p - i * a.W;  // (only the H1 terms need the position)
       const float dxx = fl_dapply(x + j, a.W, i, a.H, a.ihx, a.fix_x), dxy = fl_dapply(y + j, a.W, i, a.H, a.ihx, a.fix_x);
       const float dyx = fl_dapply(x + (long long)i * a.W, 1, j, a.W, a.ihy, a.fix_y);
       const float dyy = fl_dapply(y + (long long)i * a.W, 1, j, a.W, a.ihy, a.fix_y);
-      sd += (dxx - dxy) * (dxx - dxy) + (dyx - dyy) * (dyx - dyy);
-      sy += dxy * dxy + dyy * dyy;
+      const double ex = (double)dxx - (double)dxy, ey = (double)dyx - (double)dyy;
+      sd += ex * ex + ey * ey;
+      sy += (double)dxy * (double)dxy + (double)dyy * (double)dyy;
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    sd += __shfl_xor(sd, off, 64);
-    sy += __shfl_xor(sy, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = sd, red[1][threadIdx.x >> 6] = sy;
+  red[0][threadIdx.x] = sd, red[1][threadIdx.x] = sy;
   __syncthreads();
-  if (threadIdx.x < 2) a.sums[2 * r + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+  for (int half = 128; half >= 1; half >>= 1) {  // a fixed tree
+    if ((int)threadIdx.x < half) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + half];
+      red[1][threadIdx.x] += red[1][threadIdx.x + half];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 2) a.sums[2 * r + threadIdx.x] = red[threadIdx.x][0];
 }
 
 struct FieldFinishArgs {
-  const float* sums;
+  const double* sums;
   float* loss;     // [1]
   float* rowcoef;  // [rows] or null
   int rows, mode;
@@ -89,34 +95,40 @@ struct FieldFinishArgs {
 
 // one workgroup: the rows' terms in index order, loss = coef * sum, and the adjoint coefficient of every row
 __global__ void __launch_bounds__(64) field_finish_kernel(FieldFinishArgs a) {
-  float part = 0.f;
+  __shared__ double parts[64];
+  double part = 0.;
+  const double c = (double)a.abs_const;
   for (int r = threadIdx.x; r < a.rows; r += 64) {
-    const float sd = a.sums[2 * r], sy = a.sums[2 * r + 1];
-    float term, ar;
+    const double sd = a.sums[2 * r], sy = a.sums[2 * r + 1];
+    double term, ar;
     if (a.mode == 0) {  // rel: sqrt(sd) / sqrt(sy)
-      const float nd = sqrtf(sd), ny = sqrtf(sy);
+      const double nd = sqrt(sd), ny = sqrt(sy);
       term = nd / ny;
-      ar = 1.f / (nd * ny);
+      ar = 1. / (nd * ny);
     } else if (a.mode == 1) {  // abs: sqrt(c sd)
-      term = sqrtf(a.abs_const * sd);
-      ar = a.abs_const / term;
+      term = sqrt(c * sd);
+      ar = c / term;
     } else if (a.mode == 2) {  // sq
       term = sd;
-      ar = 2.f;
+      ar = 2.;
     } else if (a.mode == 3) {  // rel, p = 1: sum|e| / sum|y|   (the adjoint field is sign(e))
       term = sd / sy;
-      ar = 1.f / sy;
+      ar = 1. / sy;
     } else {  // abs, p = 1: c sum|e|
-      term = a.abs_const * sd;
-      ar = a.abs_const;
+      term = c * sd;
+      ar = c;
     }
     part += term;
-    if (a.rowcoef != nullptr) a.rowcoef[r] = a.coef * ar;
+    if (a.rowcoef != nullptr) a.rowcoef[r] = (float)((double)a.coef * ar);
   }
-  // lanes hold interleaved rows: sum them in lane order (fixed shape)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-  if (threadIdx.x == 0) a.loss[0] = a.coef * part;
+  // lanes hold interleaved rows: sum them in lane order
+  parts[threadIdx.x] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double total = 0.;
+    for (int l = 0; l < 64; ++l) total += parts[l];
+    a.loss[0] = (float)((double)a.coef * total);
+  }
 }
 
 // gx = rowcoef (e + Dx^T Dx e + Dy^T Dy e)
@@ -162,7 +174,7 @@ static int fl_check(int rows, int H, int W, int order, const void* x, const void
 }
 
 extern "C" int ppsci_field_loss_sums(int rows, int H, int W, int order, float ihx, float ihy, int fix_x, int fix_y, const float* x,
-                                     const float* y, float* sums, void* stream) {
+                                     const float* y, double* sums, void* stream) {
   if (fl_check(rows, H, W, order, x, y) != PPSCI_OK || !sums) {
     ppsci_set_error("field_loss_sums: invalid argument");
     return PPSCI_E_INVALID;
@@ -176,7 +188,7 @@ extern "C" int ppsci_field_loss_sums(int rows, int H, int W, int order, float ih
   return PPSCI_OK;
 }
 
-extern "C" int ppsci_field_loss_finish(int rows, int mode, float abs_const, float coef, const float* sums, float* loss,
+extern "C" int ppsci_field_loss_finish(int rows, int mode, float abs_const, float coef, const double* sums, float* loss,
                                        float* rowcoef, void* stream) {
   if (rows < 1 || mode < 0 || mode > 4 || !sums || !loss) {
     ppsci_set_error("field_loss_finish: invalid argument");

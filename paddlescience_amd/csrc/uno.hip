@@ -141,3 +141,6 @@ extern "C" int ppsci_resample2d(int n, int H, int W, int H2, int W2, const float
 
 // ---- the Laplace neural operator's kernels (a file of their own; this unit is their translation unit)
 #include "lno.inc"
+
+// ---- the 1-D Fourier neural operator of Geo-FNO (ppsci.arch.FNO1d), likewise
+#include "fno1d.inc"

@@ -31,7 +31,8 @@ class FieldLossPlan:
         key = (rows, x.device)
         if key not in self._buf:
             f = dict(dtype=torch.float32, device=x.device)
-            self._buf[key] = (torch.empty(2 * rows, **f), torch.empty(1, **f), torch.empty(rows, **f))
+            # (the row sums are doubles: the kernels carry sums, terms and total in double and round once, at the loss)
+            self._buf[key] = (torch.empty(2 * rows, dtype=torch.float64, device=x.device), torch.empty(1, **f), torch.empty(rows, **f))
         return self._buf[key]
 
     def value(self, x: torch.Tensor, y: torch.Tensor, coef: float, want_adjoint: bool = False):

@@ -122,12 +122,17 @@ class OperatorEngine:
 
         self._step_graph = StepGraph(self.grad.is_cuda and os.environ.get("PPSCI_HIP_GRAPH", "1") != "0")
         # forward and backward on this framework's own kernels, no autograd graph of the network (fno_engine.py)
-        from . import fno_engine, lno_engine, uno_engine
+        from . import fno_engine, geofno_engine, lno_engine, uno_engine
 
-        why = fno_engine.supports(model)
-        if why is not None and uno_engine.supports(model) is not None and lno_engine.supports(model) is not None:
-            raise NotImplementedError(f"operator engine: {why}")
-        self.native = model.native()  # fno_engine.FnoNative / uno_engine.UnoNative / lno_engine.LnoNative
+        whys = []
+        for executor in (fno_engine, uno_engine, lno_engine, geofno_engine):
+            whys.append(executor.supports(model))
+            if whys[-1] is None:
+                break
+        else:
+            raise NotImplementedError(f"operator engine: {whys[0]}")
+        # fno_engine.FnoNative / uno_engine.UnoNative / lno_engine.LnoNative / geofno_engine.Fno1dNative
+        self.native = model.native()
 
     def _forward_backward_eager(self, constraints: List[OperatorConstraint]):
         if len(constraints) != 1:

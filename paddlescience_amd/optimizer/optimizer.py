@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from typing import Optional, Union
 
+import numpy as np
 import torch
 
 from .. import hotpath as hp
@@ -99,8 +100,11 @@ class _AdamState:
         if self.l2 != 0.0:
             # paddle Adam(weight_decay=c): L2Decay, g += c * p before the moments -- the fused kernel's l2 term with
             # the decoupled-decay factor of its AdamW branch set to 1
-            c2 = (1.0 - self.beta2 ** self.t) ** 0.5
-            lr_t = self.get_lr() * c2 / (1.0 - self.beta1 ** self.t)
+            # (bias corrections from the betas as the kernel holds them, in float32 -- what ppsci_adam_step does on its side:
+            # 1 - float32(0.999) is 1.3e-5 below 1e-3, and a correction from the exact 0.999 made every step 6e-6 too long)
+            b1, b2 = float(np.float32(self.beta1)), float(np.float32(self.beta2))
+            c2 = (1.0 - b2 ** self.t) ** 0.5
+            lr_t = self.get_lr() * c2 / (1.0 - b1 ** self.t)
             hp.optim_step(hp.OPT_ADAMW, self.model.flat_params, grad, [self.m, self.v],
                           [lr_t, grad_scale, self.l2, self.beta1, self.epsilon * c2, 1.0, self.beta2])
         else:
