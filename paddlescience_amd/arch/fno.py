@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import base
+from .operator_base import OperatorArch
 
 
 def gelu(x):
@@ -129,15 +129,27 @@ class FNOBlocks(torch.nn.Module):
         self.norm = torch.nn.ModuleList([GroupNorm1(out_channels) for _ in range(n_layers)]) if norm == "group_norm" else None
 
 
-class FNONet(base.Arch, torch.nn.Module):
+def parse_domain_padding(domain_padding, domain_padding_mode: str):
+    """DomainPadding's arguments (fno_block.py:19-140, tfnonet.py:118-127) -> ([fraction of the resolution per axis], mode), or
+    None for no padding."""
+    if domain_padding is None or (sum(domain_padding) if isinstance(domain_padding, (list, tuple)) else domain_padding) <= 0:
+        return None
+    fr = list(domain_padding) if isinstance(domain_padding, (list, tuple)) else [float(domain_padding)] * 2
+    if len(fr) != 2:
+        raise ValueError("domain_padding length must match the number of spatial dimensions (2)")
+    mode = domain_padding_mode.lower()
+    if mode not in ("one-sided", "symmetric"):
+        raise ValueError(f"Got self.padding_mode = {mode}")
+    return [float(v) for v in fr], mode
+
+
+class FNONet(OperatorArch):
     """ppsci.arch.FNONet for 2-D problems (tfnonet.py:13-193).  Input: dict with one `[B, C, H, W]` tensor per
     input key (concatenated along the channel axis, like `concat_to_tensor` with the reference's layout);
-    output: `{output_keys[0]: [B, out_channels, H, W]}`.
+    output: `{output_keys[0]: [B, out_channels, H, W]}`.  `forward_tensor`: [B, C_in, H, W] -> [B, C_out, H, W].
+    Every forward (tfnonet.py:179-193) and the backward run in fno_engine.FnoNative."""
 
-    The parameters live in ONE flat fp32 buffer (`flat_params`, module parameters are views into it) so that
-    the data-parallel all-reduce and the fused Adam kernel act on a single tensor, as for the PINN path."""
-
-    is_operator = True  # Solver: the operator engine (hand-written forward + backward, fno_engine.FnoNative)
+    _executor = "fno_engine.FnoNative"
     _conv_cls = SpectralConv2d
     spectral = "fft"  # the transform pair of the spectral branch: "fft" (rfftn / irfftn) or "sht" (SFNONet)
 
@@ -150,8 +162,7 @@ class FNONet(base.Arch, torch.nn.Module):
                  factorization: Optional[str] = None, rank: float = 1.0, joint_factorization: bool = False,
                  implementation: str = "factorized", domain_padding=None, domain_padding_mode: str = "one-sided",
                  fft_norm: str = "forward", patching_levels: int = 0, **kwargs):
-        torch.nn.Module.__init__(self)
-        base.Arch.__init__(self)
+        OperatorArch.__init__(self)
         if len(n_modes) != 2:
             raise NotImplementedError("only the 2-D spectral convolution has a HIP kernel (TFNO1dNet / TFNO3dNet)")
         for name, val, ok in (("use_mlp", use_mlp, False), ("preactivation", preactivation, False),
@@ -160,17 +171,7 @@ class FNONet(base.Arch, torch.nn.Module):
                               ("max_n_modes", max_n_modes, None)):
             if val != ok:
                 raise NotImplementedError(f"FNONet({name}={val!r}) is not built")
-        # DomainPadding (fno_block.py:19-140, tfnonet.py:118-127): per-axis fractions of the resolution, or None
-        if domain_padding is not None and (sum(domain_padding) if isinstance(domain_padding, (list, tuple)) else domain_padding) > 0:
-            fr = list(domain_padding) if isinstance(domain_padding, (list, tuple)) else [float(domain_padding)] * 2
-            if len(fr) != 2:
-                raise ValueError("domain_padding length must match the number of spatial dimensions (2)")
-            mode = domain_padding_mode.lower()
-            if mode not in ("one-sided", "symmetric"):
-                raise ValueError(f"Got self.padding_mode = {mode}")
-            self.domain_padding = ([float(v) for v in fr], mode)
-        else:
-            self.domain_padding = None
+        self.domain_padding = parse_domain_padding(domain_padding, domain_padding_mode)
         # `factorization`/`rank`: the reference's FactorizedTensor (fno_block.py:522-539) stores a DENSE complex
         # weight whatever the name says, so "Tucker" with rank 1.0 and None are the same parametrisation.
         self.input_keys, self.output_keys = tuple(input_keys), tuple(output_keys)
@@ -185,52 +186,10 @@ class FNONet(base.Arch, torch.nn.Module):
         if non_linearity not in _GELUS:
             raise NotImplementedError("non_linearity: GELU is the activation fused into the kernels")
         self.projection = ChannelMLP(hidden_channels, out_channels, projection_channels, 2, non_linearity)
-        self.flat_params: Optional[torch.Tensor] = None
-        self.flat_grad: Optional[torch.Tensor] = None
         from ..device import get_device
 
         self.to_device(get_device())
 
-    # ---- flat parameter buffer ---------------------------------------------------------------
-    def to_device(self, device):
-        """Moves the model and (re)packs every parameter as a view into `flat_params` / `flat_grad`."""
-        torch.nn.Module.to(self, device)
-        self._native = None  # (its buffers live on the old device)
-        ps = [p for p in torch.nn.Module.parameters(self)]
-        n = sum(p.numel() for p in ps)
-        flat = torch.empty(n, dtype=torch.float32, device=device)
-        grad = torch.zeros(n, dtype=torch.float32, device=device)
-        off = 0
-        for p in ps:
-            k = p.numel()
-            flat[off:off + k].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + k].view_as(p.data)
-            p.grad = grad[off:off + k].view_as(p.data)
-            off += k
-        self.flat_params, self.flat_grad = flat, grad
-        return self
-
-    def parameters(self, recurse: bool = True):
-        return list(torch.nn.Module.parameters(self, recurse))
-
-    def state_dict(self, *args, **kwargs):
-        return {k: v.detach().clone() for k, v in torch.nn.Module.state_dict(self, *args, **kwargs).items()}
-
-    def set_state_dict(self, state):
-        own = torch.nn.Module.state_dict(self)
-        with torch.no_grad():
-            for k, v in state.items():
-                own[k].copy_(torch.as_tensor(v).to(own[k].device))
-
-    def train(self, mode: bool = True):
-        torch.nn.Module.train(self, mode)
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    # ---- forward (tfnonet.py:179-193) ---------------------------------------------------------
     def padding_of(self, H: int, W: int):
         """(rows, columns, row offset, column offset) DomainPadding adds to an H x W plane: round(fraction * resolution)
         behind each axis (one-sided) or on both sides (symmetric), fno_block.py:72-115."""
@@ -239,32 +198,6 @@ class FNONet(base.Arch, torch.nn.Module):
         (fh, fw), mode = self.domain_padding
         ph, pw = round(fh * H), round(fw * W)
         return (2 * ph, 2 * pw, ph, pw) if mode == "symmetric" else (ph, pw, 0, 0)
-
-    def native(self):
-        """The kernels' executor for this model (buffers per batch shape); shared by training, eval and predict."""
-        nat = getattr(self, "_native", None)
-        if nat is None:
-            from ..fno_engine import FnoNative
-
-            nat = self._native = FnoNative(self)
-        return nat
-
-    def forward_tensor(self, x: torch.Tensor) -> torch.Tensor:
-        """[B, C_in, H, W] -> [B, C_out, H, W] (a fresh tensor; the executor owns its buffers)."""
-        return self.native().forward(x.to(dtype=torch.float32).contiguous()).clone()
-
-    def forward(self, x):
-        if self._input_transform is not None:
-            x = self._input_transform(x)
-        dev = self.flat_params.device
-        xs = [torch.as_tensor(x[k], dtype=torch.float32).to(dev) for k in self.input_keys]
-        xt = xs[0] if len(xs) == 1 else torch.cat(xs, dim=1)
-        out = {self.output_keys[0]: self.forward_tensor(xt)}
-        if self._output_transform is not None:
-            out = self._output_transform(x, out)
-        return out
-
-    __call__ = torch.nn.Module.__call__
 
 
 class TFNO2dNet(FNONet):

@@ -23,8 +23,7 @@ from typing import Tuple
 
 import torch
 
-from . import base
-from .fno import FNONet
+from .operator_base import OperatorArch
 
 HIDDEN = 128  # fc1's output features (geofno.py:153)
 
@@ -66,20 +65,16 @@ class SpectralConv1d(torch.nn.Module):
         self.weights1_imag = torch.nn.Parameter(initializer.uniform_(torch.empty(shape), 0, 1) * self.scale)
 
 
-class FNO1d(base.Arch, torch.nn.Module):
-    """ppsci.arch.FNO1d (geofno.py:95-205); constructor arguments in the reference's order.  The flat parameter buffer, state dict
-    and train / eval switches are arch/fno.FNONet's (the same functions; FNO1d is not an FNONet)."""
+class FNO1d(OperatorArch):
+    """ppsci.arch.FNO1d (geofno.py:95-205); constructor arguments in the reference's order.  `forward_tensor`:
+    [B, s, input_channel] -> [B, output_np, 1]."""
 
-    is_operator = True  # Solver: the operator engine (hand-written forward + backward, geofno_engine.Fno1dNative)
+    _executor = "geofno_engine.Fno1dNative"
     channel_axis = -1  # input keys are concatenated along the LAST axis (channel-last fields)
-    to_device, parameters, state_dict, set_state_dict = FNONet.to_device, FNONet.parameters, FNONet.state_dict, FNONet.set_state_dict
-    train, eval = FNONet.train, FNONet.eval
-    __call__ = torch.nn.Module.__call__
 
     def __init__(self, input_key: Tuple[str, ...] = ("input",), output_key: Tuple[str, ...] = ("output",), modes: int = 64,
                  width: int = 64, padding: int = 100, input_channel: int = 2, output_np: int = 2001):
-        torch.nn.Module.__init__(self)
-        base.Arch.__init__(self)
+        OperatorArch.__init__(self)
         self.input_keys, self.output_keys = tuple(input_key), tuple(output_key)
         if len(self.output_keys) != 1:
             raise NotImplementedError("FNO1d with more than one output key: fc2 has one output feature")
@@ -96,30 +91,6 @@ class FNO1d(base.Arch, torch.nn.Module):
             setattr(self, f"w{k}", _Conv1(self.width, self.width))
         self.fc1 = _Linear(self.width, HIDDEN)
         self.fc2 = _Linear(HIDDEN, 1)
-        self.flat_params = self.flat_grad = None
         from ..device import get_device
 
         self.to_device(get_device())
-
-    def native(self):
-        nat = getattr(self, "_native", None)
-        if nat is None:
-            from ..geofno_engine import Fno1dNative
-
-            nat = self._native = Fno1dNative(self)
-        return nat
-
-    def forward_tensor(self, x: torch.Tensor) -> torch.Tensor:
-        """[B, s, input_channel] -> [B, output_np, 1] (a fresh tensor; the executor owns its buffers)."""
-        return self.native().forward(x.to(dtype=torch.float32).contiguous()).clone()
-
-    def forward(self, x):
-        if self._input_transform is not None:
-            x = self._input_transform(x)
-        dev = self.flat_params.device
-        xs = [torch.as_tensor(x[k], dtype=torch.float32).to(dev) for k in self.input_keys]
-        xt = xs[0] if len(xs) == 1 else torch.cat(xs, dim=-1)
-        out = {self.output_keys[0]: self.forward_tensor(xt)}
-        if self._output_transform is not None:
-            out = self._output_transform(x, out)
-        return out

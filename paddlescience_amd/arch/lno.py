@@ -21,8 +21,7 @@ import numpy as np
 import torch
 
 from . import activation as act_mod
-from . import base
-from .fno import FNONet
+from .operator_base import OperatorArch
 
 # the activations of arch/activation.py that lno_head_* evaluates (no trainable activation parameters in the head kernel)
 HEAD_ACTIVATIONS = ("tanh", "silu", "sin", "cos", "sigmoid", "gelu", "relu", "leaky_relu", "elu", "selu", "identity")
@@ -88,21 +87,17 @@ class Laplace(torch.nn.Module):
         self.weights_pole_imag = torch.nn.ParameterList(pi)
 
 
-class LNO(base.Arch, torch.nn.Module):
-    """ppsci.arch.LNO (lno.py:190-313); constructor arguments in the reference's order.  The flat parameter buffer, state dict
-    and train / eval switches are arch/fno.FNONet's (the same functions; LNO is not an FNONet)."""
+class LNO(OperatorArch):
+    """ppsci.arch.LNO (lno.py:190-313); constructor arguments in the reference's order.  `forward_tensor`:
+    [B, n1, n2, n3, data channels] -> [B, n1, n2, n3, 1]."""
 
-    is_operator = True  # Solver: the operator engine (hand-written forward + backward, lno_engine.LnoNative)
+    _executor = "lno_engine.LnoNative"
     channel_axis = -1  # input keys are concatenated along the LAST axis (channel-last fields)
-    to_device, parameters, state_dict, set_state_dict = FNONet.to_device, FNONet.parameters, FNONet.state_dict, FNONet.set_state_dict
-    train, eval = FNONet.train, FNONet.eval
-    __call__ = torch.nn.Module.__call__
 
     def __init__(self, input_keys: Tuple[str, ...], output_keys: Tuple[str, ...], width: int, modes: Tuple[int, ...], T,
                  data: Optional[Tuple] = None, in_features: int = 1, hidden_features: int = 64, activation: str = "sin",
                  use_norm: bool = True, use_grid: bool = False):
-        torch.nn.Module.__init__(self)
-        base.Arch.__init__(self)
+        OperatorArch.__init__(self)
         self.input_keys, self.output_keys = tuple(input_keys), tuple(output_keys)
         self.width, self.modes, self.dims = int(width), tuple(int(v) for v in modes), len(modes)
         assert self.dims <= 3, "Only 3 dims and lower of modes are supported now."
@@ -128,30 +123,6 @@ class LNO(base.Arch, torch.nn.Module):
         self.conv = _Conv1(self.width, self.width)
         self.fc1 = _Linear(self.width, self.hidden_features)
         self.fc2 = _Linear(self.hidden_features, 1)
-        self.flat_params = self.flat_grad = None
         from ..device import get_device
 
         self.to_device(get_device())
-
-    def native(self):
-        nat = getattr(self, "_native", None)
-        if nat is None:
-            from ..lno_engine import LnoNative
-
-            nat = self._native = LnoNative(self)
-        return nat
-
-    def forward_tensor(self, x: torch.Tensor) -> torch.Tensor:
-        """[B, n1, n2, n3, data channels] -> [B, n1, n2, n3, 1] (a fresh tensor; the executor owns its buffers)."""
-        return self.native().forward(x.to(dtype=torch.float32).contiguous()).clone()
-
-    def forward(self, x):
-        if self._input_transform is not None:
-            x = self._input_transform(x)
-        dev = self.flat_params.device
-        xs = [torch.as_tensor(x[k], dtype=torch.float32).to(dev) for k in self.input_keys]
-        xt = xs[0] if len(xs) == 1 else torch.cat(xs, dim=-1)
-        out = {self.output_keys[0]: self.forward_tensor(xt)}
-        if self._output_transform is not None:
-            out = self._output_transform(x, out)
-        return out

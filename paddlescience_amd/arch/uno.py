@@ -22,8 +22,8 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import base
 from . import fno as F
+from .operator_base import OperatorArch
 
 
 class UNOBlock(torch.nn.Module):
@@ -46,7 +46,10 @@ class UNOBlock(torch.nn.Module):
 
 class UNONet(F.FNONet):
     """ppsci.arch.UNONet for 2-D problems (unonet.py:14-289); constructor arguments in the reference's order.  The flat
-    parameter buffer, state dict, `forward` on dicts etc. are FNONet's."""
+    parameter buffer, state dict, `forward` on dicts etc. are FNONet's (operator_base.OperatorArch).  `forward_tensor`:
+    [B, C_in, H, W] -> [B, C_out, H', W'], the grid scaled end to end."""
+
+    _executor = "uno_engine.UnoNative"
 
     def __init__(self, input_keys: Tuple[str, ...], output_keys: Tuple[str, ...], in_channels: int, out_channels: int,
                  hidden_channels: int, lifting_channels: int = 256, projection_channels: int = 256, n_layers: int = 4,
@@ -57,8 +60,7 @@ class UNONet(F.FNONet):
                  rank: float = 1.0, joint_factorization: bool = False, implementation: str = "factorized",
                  domain_padding=None, domain_padding_mode: str = "one-sided", fft_norm: str = "forward",
                  patching_levels: int = 0, **kwargs):
-        torch.nn.Module.__init__(self)
-        base.Arch.__init__(self)
+        OperatorArch.__init__(self)
         if uno_out_channels is None:
             raise ValueError("uno_out_channels can not be None")
         if uno_n_modes is None:
@@ -89,16 +91,7 @@ class UNONet(F.FNONet):
             raise NotImplementedError(f"horizontal_skip={horizontal_skip!r} (built: 'linear')")
         if fft_norm not in ("forward", "backward", "ortho"):
             raise ValueError(f"fft_norm={fft_norm!r}")
-        if domain_padding is not None and (sum(domain_padding) if isinstance(domain_padding, (list, tuple)) else domain_padding) > 0:
-            fr = list(domain_padding) if isinstance(domain_padding, (list, tuple)) else [float(domain_padding)] * 2
-            if len(fr) != 2:
-                raise ValueError("domain_padding length must match the number of spatial dimensions (2)")
-            mode = domain_padding_mode.lower()
-            if mode not in ("one-sided", "symmetric"):
-                raise ValueError(f"Got self.padding_mode = {mode}")
-            self.domain_padding = ([float(v) for v in fr], mode)
-        else:
-            self.domain_padding = None
+        self.domain_padding = F.parse_domain_padding(domain_padding, domain_padding_mode)
         self.input_keys, self.output_keys = tuple(input_keys), tuple(output_keys)
         self.in_channels, self.out_channels, self.hidden_channels = in_channels, out_channels, hidden_channels
         self.n_layers, self.fft_norm = n_layers, fft_norm
@@ -129,15 +122,6 @@ class UNONet(F.FNONet):
             prev = self.uno_out_channels[i]
         self.fno_blocks = torch.nn.ModuleList(blocks)
         self.projection = F.ChannelMLP(prev, out_channels, projection_channels, 2, non_linearity)
-        self.flat_params = self.flat_grad = None
         from ..device import get_device
 
         self.to_device(get_device())
-
-    def native(self):
-        nat = getattr(self, "_native", None)
-        if nat is None:
-            from ..uno_engine import UnoNative
-
-            nat = self._native = UnoNative(self)
-        return nat

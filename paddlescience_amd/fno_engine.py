@@ -29,6 +29,7 @@ from . import _lib as L
 from . import hotpath as hp
 from .arch import fno as fno_arch
 from .hotpath import _p, _stream_ptr
+from .native_executor import NativeExecutor, grads_adjacent
 
 
 def supports(model) -> Optional[str]:
@@ -59,22 +60,14 @@ def _virtual(mode, x0=None, W0=None, b0=None):
     return v
 
 
-class FnoNative:
+class FnoNative(NativeExecutor):
+    """Buffer sets per input shape (batch, H, W), `backward`, the deferred weight-gradient sums: native_executor.NativeExecutor."""
+
+    label, supports = "FNO", staticmethod(supports)
+    EXECUTOR_ATTRS = NativeExecutor.EXECUTOR_ATTRS + ("use_side", "_side")
+
     def __init__(self, model):
-        why = supports(model)
-        if why is not None:
-            raise NotImplementedError(f"native FNO path: {why}")
-        self.m = model
-        self.shape = None
-        # One buffer set per input shape (batch, H, W), kept alive: training, evaluation and prediction share this executor
-        # (arch/fno.py), the reference's TFNO config trains at 16 x 16 and evaluates at 32 x 32 with eval_during_train, a ragged
-        # last eval batch changes the batch size -- and the operator engine REPLAYS a captured HIP graph of the training step
-        # that holds the training buffers' addresses.  Handing those back to the caching allocator when another shape comes by
-        # would leave the graph writing through stale pointers.  At most `max_sets` sets are kept (least recently used out);
-        # dropping one bumps `generation`, which is part of the engine's graph key, so no captured step outlives its buffers.
-        self._sets = {}
-        self.max_sets = 8
-        self.generation = 0
+        super().__init__(model)
         # A TFNO step is ~57 kernels of 5-17 us, most of them a dependent chain -- but not all: a block's skip convolution does
         # not depend on its spectral branch (forward), and no weight gradient is needed before the end of the backward pass.
         # PPSCI_FNO_SIDE_STREAM=1 puts those launches onto a second HIP stream, forked from and joined back into the launch stream
@@ -102,28 +95,6 @@ class FnoNative:
             torch.cuda.current_stream().wait_stream(self._side)
 
     # ------------------------------------------------------------------ buffers
-    def _switch(self, B: int, H: int, W: int) -> None:
-        keep = ("m", "shape", "_sets", "max_sets", "generation", "use_side", "_side", "defer_wgrad_sums")
-        return self._switch_(B, H, W, keep)
-
-    def _switch_(self, B: int, H: int, W: int, keep) -> None:
-        """Make the buffer set of input shape (B, H, W) the current one (allocating it on first use); the previous set stays
-        alive under its own key."""
-        if self.shape is not None:
-            self._sets[self.shape] = {k: v for k, v in self.__dict__.items() if k not in keep}
-        self.shape = None  # no current set until the new one is complete: a failed allocation leaves the executor usable
-        for k in [k for k in self.__dict__ if k not in keep]:
-            del self.__dict__[k]
-        key = (B, H, W)
-        if key in self._sets:
-            self.__dict__.update(self._sets.pop(key))  # (re-inserted when it is switched away from: most recently used last)
-            self.shape = key
-            return
-        while len(self._sets) >= self.max_sets:
-            self._sets.pop(next(iter(self._sets)))
-            self.generation += 1
-        self._alloc(B, H, W)
-
     def _alloc(self, B: int, H: int, W: int) -> None:
         m = self.m
         dev = m.flat_params.device
@@ -135,7 +106,6 @@ class FnoNative:
         H, W = H0 + ah, W0 + aw
         self.padded = bool(ah or aw)
         P, P0 = H * W, H0 * W0
-        self.shape = (B, H0, W0)
         self.hw, self.hw0 = (H, W), (H0, W0)
         self.P, self.P0 = P, P0
         lift, proj = m.lifting.fcs, m.projection.fcs
@@ -207,7 +177,7 @@ class FnoNative:
             self.gz2 = self.ga.view(-1)[:B * self.c_proj * P0].view(B, self.c_proj, P0)
         self.gv = torch.empty((B, Ch, P), **f)
         self._wbufs: List[torch.Tensor] = []  # per-chunk partials of the weight gradients, one buffer per _wgrad call of a pass
-        self._wcall, self._wsegs = 0, []
+        self._wcall = 0
         self.desc = L.SpectralDesc()
         d = self.desc
         d.batch, d.c_in, d.c_out, d.h, d.wf, d.modes_x, d.modes_y = B, Ch, Ch, H, Wf, mx, my
@@ -225,7 +195,7 @@ class FnoNative:
         m = self.m
         B, _, H0, W0 = x.shape
         if self.shape != (B, H0, W0):
-            self._switch(B, H0, W0)
+            self._switch((B, H0, W0))
         P, P0, Ch, nl = self.P, self.P0, m.hidden_channels, m.n_layers
         H, W = self.hw
         self.x_in = x.contiguous().view(B, m.in_channels, P0)
@@ -321,7 +291,7 @@ class FnoNative:
     # ------------------------------------------------------------------ backward
     def _partials(self, n: int) -> torch.Tensor:
         """The next per-chunk partial buffer of this backward pass (every weight gradient keeps its own until the one
-        reduction launch at the end: self._flush_wgrads)."""
+        reduction launch at the end: flush_wgrads)."""
         i = self._wcall
         self._wcall += 1
         if i == len(self._wbufs):
@@ -338,7 +308,7 @@ class FnoNative:
     def _wgrad_(self, B, ci, co, P, x, gy, w_param, b_param, xv=None) -> None:
         chunks = int(L.lib().ppsci_pw_conv_wgrad_chunks(B, P))  # (P differs between the padded blocks and lifting / projection)
         wg = w_param.grad.view(-1)
-        if b_param is not None and b_param.grad.data_ptr() == wg.data_ptr() + 4 * co * ci:
+        if b_param is not None and grads_adjacent(w_param, b_param):
             # weight and bias gradients are neighbours in the flat buffer: partial rows [Co*Ci | Co], ONE fixed-order sum
             ld = co * ci + co
             part = self._partials(chunks * ld)
@@ -361,8 +331,7 @@ class FnoNative:
         K0, C1 = m.in_channels, self.c_lift
         return (self.lift_virtual and os.environ.get("PPSCI_FNO_LIFT0_FUSED", "1") != "0" and K0 <= 4 and Ch <= 32 and Ch % 4 == 0
                 and b0 is not None and b1 is not None and os.environ.get("PPSCI_FNO_LIFT1_FUSED", "1") != "0"
-                and b0.grad.data_ptr() == w0.grad.view(-1).data_ptr() + 4 * C1 * K0
-                and b1.grad.data_ptr() == w1.grad.view(-1).data_ptr() + 4 * Ch * C1)
+                and grads_adjacent(w0, b0) and grads_adjacent(w1, b1))
 
     def _lift_takes_addend(self, Ch) -> bool:
         """The lifting kernel is the ONLY consumer of dL/dx_0 (both lifting gradients from it, no padding in between)."""
@@ -377,11 +346,11 @@ class FnoNative:
         K0, C1 = m.in_channels, self.c_lift
         w0, b0 = lift[0].weight, lift[0].bias
         if (os.environ.get("PPSCI_FNO_LIFT0_FUSED", "1") == "0" or K0 > 4 or Ch > 64 or Ch % 4 != 0 or b0 is None
-                or b0.grad.data_ptr() != w0.grad.view(-1).data_ptr() + 4 * C1 * K0):
+                or not grads_adjacent(w0, b0)):
             return False
         w1, b1 = lift[1].weight, lift[1].bias
         # the second layer's gradient from the same pass (GELU(z1) is at hand there) when its weight and bias gradients are neighbours
-        both = (Ch <= 32 and b1 is not None and b1.grad.data_ptr() == w1.grad.view(-1).data_ptr() + 4 * Ch * C1
+        both = (Ch <= 32 and b1 is not None and grads_adjacent(w1, b1)
                 and os.environ.get("PPSCI_FNO_LIFT1_FUSED", "1") != "0")
         if not both:
             self._wgrad(B, C1, Ch, P0, None, gx, w1, b1, xv=self.a1_virtual)
@@ -400,21 +369,7 @@ class FnoNative:
                 self._wsegs.append((part1.data_ptr(), w1.grad.view(-1).data_ptr(), chunks, ld1))
         return True
 
-    defer_wgrad_sums = False  # backward() leaves the partials of the weight gradients unsummed (self._wsegs) when set
-
-    def _flush_wgrads(self) -> None:
-        """ONE launch sums the per-chunk partials of every weight gradient of the pass (ppsci_reduce_rows_multi; up to 16
-        segments per launch): eight reductions of ~5 us each were launch latency, not work."""
-        st = _stream_ptr(self.y)
-        for i0 in range(0, len(self._wsegs), 16):
-            batch = self._wsegs[i0:i0 + 16]
-            arr = (L.ReduceSeg * len(batch))()
-            for k, (src, dst, rows, cols) in enumerate(batch):
-                arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
-            L.check(L.lib().ppsci_reduce_rows_multi(len(batch), arr, st))
-        self._wsegs = []
-
-    def backward(self, gy: torch.Tensor) -> None:
+    def _backward(self, gy: torch.Tensor) -> None:
         """gy = dL/dy [B, C_out, H, W]; writes dL/d(parameter) into every parameter's `.grad` (views of flat_grad)."""
         m = self.m
         B = self.shape[0]
@@ -423,7 +378,7 @@ class FnoNative:
         lift, proj, fb = m.lifting.fcs, m.projection.fcs, m.fno_blocks
         gy = gy.contiguous().view(B, m.out_channels, P0)
         st = _stream_ptr(self.y)
-        self._wcall, self._wsegs = 0, []
+        self._wcall = 0
         # projection: y = W2 gelu(z2) + b2, z2 = W1 x_out + b1
         self._wgrad(B, self.c_proj, m.out_channels, P0, self.z2, gy, proj[1].weight, proj[1].bias, xv=self.gelu_on_load)
         gz2 = self.gz2
@@ -534,5 +489,3 @@ class FnoNative:
         else:
             self._wgrad(B, m.in_channels, Ch, P0, self.x_in, gx, lift[0].weight, lift[0].bias)
         self._join()  # every weight gradient's partial rows are complete
-        if not self.defer_wgrad_sums:
-            self._flush_wgrads()  # (deferred: the caller sums them together with its Adam update, operator_engine)

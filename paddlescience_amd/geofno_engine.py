@@ -26,18 +26,19 @@ With C = width, M = modes, s the input length, L = s + padding, n = output_np, t
 Both v_k and x_{k+1} = gelu(v_k) are stored: the reverse pass needs v_k for gelu' and x_k for the convolution's weight gradient, and
 the next layer reads x_{k+1} twice (analysis, layer), so recomputing the erf on load would cost three evaluations per element to
 save one 4 B write.  The partial rows are summed by ONE ppsci_reduce_rows_multi launch (fixed order: gradients are bitwise
-repeatable).  The contract is fno_engine.FnoNative's (`forward`, `backward`, `gx`, `generation`, one buffer set per input shape
-kept alive, `defer_wgrad_sums` / `_wsegs`)."""
+repeatable).  The contract is native_executor.NativeExecutor's (`forward`, `backward`, `gx`, `generation`, one buffer set per
+input shape kept alive, the deferred weight-gradient sums)."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from .hotpath import _p, _require_device, _stream_ptr
+from .native_executor import NativeExecutor, grads_adjacent
 
 WGRAD_CHUNK = 256   # points per partial row of the dense weight gradients (ppsci_fno1d_wgrad)
 ANA_WORKGROUPS = 256  # the analysis GEMM splits its K axis until it launches about this many workgroups
@@ -86,35 +87,10 @@ def interp_tables(s: int, n: int):
     return i0.astype(np.int32), t.astype(np.float32), first.astype(np.int32)
 
 
-class Fno1dNative:
-    def __init__(self, model):
-        why = supports(model)
-        if why is not None:
-            raise NotImplementedError(f"native FNO1d path: {why}")
-        self.m = model
-        self.shape = None
-        self._sets = {}  # one buffer set per input shape, kept alive under a replayed graph (see fno_engine.FnoNative)
-        self.max_sets = 8
-        self.generation = 0
-        self.defer_wgrad_sums = False
-        self._wsegs: List[tuple] = []
+class Fno1dNative(NativeExecutor):
+    """Buffer sets per input shape (batch, s), `backward`, the deferred weight-gradient sums: native_executor.NativeExecutor."""
 
-    _KEEP = ("m", "shape", "_sets", "max_sets", "generation", "defer_wgrad_sums", "_wsegs")
-
-    def _switch(self, key) -> None:
-        if self.shape is not None:
-            self._sets[self.shape] = {k: v for k, v in self.__dict__.items() if k not in self._KEEP}
-        self.shape = None
-        for k in [k for k in self.__dict__ if k not in self._KEEP]:
-            del self.__dict__[k]
-        if key in self._sets:
-            self.__dict__.update(self._sets.pop(key))
-            self.shape = key
-            return
-        while len(self._sets) >= self.max_sets:
-            self._sets.pop(next(iter(self._sets)))
-            self.generation += 1
-        self._alloc(*key)
+    label, supports = "FNO1d", staticmethod(supports)
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int, s: int) -> None:
@@ -163,9 +139,8 @@ class Fno1dNative:
         self.lift_rows = int(L.lib().ppsci_fno1d_point_rows(B * s))
         self.p_lift = torch.empty((self.lift_rows, m.input_channel * Cw + Cw), **f)
         for mod in [m.fc0, m.fc1, m.fc2] + [getattr(m, f"w{k}") for k in range(4)]:
-            if mod.bias.grad.data_ptr() != mod.weight.grad.data_ptr() + mod.weight.numel() * 4:
+            if not grads_adjacent(mod.weight, mod.bias):
                 raise RuntimeError("FNO1d: a layer's weight and bias gradients are not contiguous in the flat buffer")
-        self.shape = (B, s)
 
     @staticmethod
     def _slices(rows: int, K: int) -> int:
@@ -221,7 +196,7 @@ class Fno1dNative:
         return self.y.view(B, n, 1)
 
     # ------------------------------------------------------------------ backward
-    def backward(self, gy: torch.Tensor) -> None:
+    def _backward(self, gy: torch.Tensor) -> None:
         """gy = dL/dy [B, output_np, 1]; writes dL/d(parameter) into every parameter's `.grad` (views of flat_grad) and dL/dx
         into `self.gx` [B, s, input_channel]."""
         m, lib = self.m, L.lib()
@@ -229,7 +204,6 @@ class Fno1dNative:
         Cw, M, Hd = m.width, m.modes1, m.hidden_features
         gy = gy.contiguous().view(B, n)
         st = _stream_ptr(self.y)
-        self._wsegs = []
         L.check(lib.ppsci_fno1d_head_pre(B, Hd, n, _p(self.z), _p(gy), _p(m.fc2.weight), _p(self.gz), _p(self.p_fc2), st))
         self._wsegs.append((self.p_fc2.data_ptr(), m.fc2.weight.grad.data_ptr(), self.p_fc2.shape[0], Hd + 1))
         self._layer(st, R=Cw, K1=0, K2=Hd, A2=m.fc1.weight, a2_rs=Hd, a2_cs=1, X2=self.gz, x2_bs=Hd * n, x2_ld=n, x2_len=n, out=self.gu,
@@ -261,16 +235,3 @@ class Fno1dNative:
         L.check(lib.ppsci_fno1d_lift_bwd(B, s, Lp, m.input_channel, Cw, _p(self.x_in), _p(m.fc0.weight), _p(gv), _p(self.gx),
                                          _p(self.p_lift), st))
         self._wsegs.append((self.p_lift.data_ptr(), m.fc0.weight.grad.data_ptr(), self.lift_rows, self.p_lift.shape[1]))
-        if not self.defer_wgrad_sums:
-            self._flush_wgrads()
-
-    def _flush_wgrads(self) -> None:
-        """ONE launch sums every partial-row matrix of the pass (ppsci_reduce_rows_multi, up to 16 segments per launch)."""
-        st = _stream_ptr(self.y)
-        for i0 in range(0, len(self._wsegs), 16):
-            batch = self._wsegs[i0:i0 + 16]
-            arr = (L.ReduceSeg * len(batch))()
-            for k, (src, dst, rows, cols) in enumerate(batch):
-                arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
-            L.check(L.lib().ppsci_reduce_rows_multi(len(batch), arr, st))
-        self._wsegs = []

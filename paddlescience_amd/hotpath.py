@@ -303,6 +303,23 @@ def reduce_rows(partials: torch.Tensor, rows: int, cols: int, out: torch.Tensor,
     L.check(L.lib().ppsci_reduce_rows(_p(partials), rows, cols, _p(out), 1 if accumulate else 0, _stream_ptr(out)))
 
 
+def _reduce_segs(segs: Sequence[tuple]):
+    """The C array of (source pointer, destination pointer, rows, cols) row reductions (L.ReduceSeg, overwriting)."""
+    arr = (L.ReduceSeg * len(segs))()
+    for k, (src, dst, rows, cols) in enumerate(segs):
+        arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
+    return arr
+
+
+def reduce_rows_multi(segs: Sequence[tuple], like: torch.Tensor) -> None:
+    """ppsci_reduce_rows_multi: segs = (source pointer, destination pointer, rows, cols) -- several row reductions with different
+    destinations in ONE launch per 16 segments, on the launch stream of `like`'s device."""
+    st = _stream_ptr(like)
+    for i0 in range(0, len(segs), 16):
+        batch = segs[i0:i0 + 16]
+        L.check(L.lib().ppsci_reduce_rows_multi(len(batch), _reduce_segs(batch), st))
+
+
 def reduce_rows_multi_adam(segs: Sequence[tuple], params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
                            lr: float, step_t: int, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                            grad_scale: float = 1.0) -> None:
@@ -311,10 +328,7 @@ def reduce_rows_multi_adam(segs: Sequence[tuple], params: torch.Tensor, grad: to
     _require_device(params)
     _chk_f32(params, grad, m, v)
     note_param_write()
-    arr = (L.ReduceSeg * len(segs))()
-    for k, (src, dst, rows, cols) in enumerate(segs):
-        arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
-    L.check(L.lib().ppsci_reduce_rows_multi_adam(len(segs), arr, params.numel(), _p(params), _p(grad), _p(m), _p(v), lr, beta1,
+    L.check(L.lib().ppsci_reduce_rows_multi_adam(len(segs), _reduce_segs(segs), params.numel(), _p(params), _p(grad), _p(m), _p(v), lr, beta1,
                                                  beta2, eps, step_t, grad_scale, _stream_ptr(params)))
 
 

@@ -29,17 +29,18 @@ E_d[pair][m][s] = exp(mu_d[pair][m] t_d[s]) (ppsci_lno_tables), z the Laplace la
 
 The three dL/dmu contributions land in rows [0, B), [B, 2B) and 2B of one partial matrix per pole tensor; those, the head's and
 fc0's partial rows are summed by ONE ppsci_reduce_rows_multi launch (fixed order: gradients are bitwise repeatable).  The
-contract is fno_engine.FnoNative's (`forward`, `backward`, `generation`, one buffer set per input shape kept alive)."""
+contract is native_executor.NativeExecutor's (`forward`, `backward`, `gx`, `generation`, one buffer set per input shape kept alive)."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from .hotpath import _p, _require_device, _stream_ptr
+from .native_executor import NativeExecutor, grads_adjacent
 
 
 def supports(model) -> Optional[str]:
@@ -65,35 +66,10 @@ def twiddles(ns) -> np.ndarray:
     return np.concatenate(rows, 0).astype(np.float32)
 
 
-class LnoNative:
-    def __init__(self, model):
-        why = supports(model)
-        if why is not None:
-            raise NotImplementedError(f"native LNO path: {why}")
-        self.m = model
-        self.shape = None
-        self._sets = {}  # one buffer set per input shape, kept alive under a replayed graph (see fno_engine.FnoNative)
-        self.max_sets = 8
-        self.generation = 0
-        self.defer_wgrad_sums = False
-        self._wsegs: List[tuple] = []
+class LnoNative(NativeExecutor):
+    """Buffer sets per input shape (batch, n1, n2, n3), `backward`, the deferred weight-gradient sums: native_executor.NativeExecutor."""
 
-    _KEEP = ("m", "shape", "_sets", "max_sets", "generation", "defer_wgrad_sums", "_wsegs")
-
-    def _switch(self, key) -> None:
-        if self.shape is not None:
-            self._sets[self.shape] = {k: v for k, v in self.__dict__.items() if k not in self._KEEP}
-        self.shape = None
-        for k in [k for k in self.__dict__ if k not in self._KEEP]:
-            del self.__dict__[k]
-        if key in self._sets:
-            self.__dict__.update(self._sets.pop(key))
-            self.shape = key
-            return
-        while len(self._sets) >= self.max_sets:
-            self._sets.pop(next(iter(self._sets)))
-            self.generation += 1
-        self._alloc(*key)
+    label, supports = "LNO", staticmethod(supports)
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int, n1: int, n2: int, n3: int) -> None:
@@ -149,15 +125,10 @@ class LnoNative:
         self.p_head = torch.empty((self.rows, CC + Cw + Cw * Hd + 2 * Hd + 1), **f)
         self.gx = torch.empty((B, N, self.fd), **f)
         # the six head tensors are summed as ONE row segment: they follow each other in the flat gradient buffer
-        heads = [m.conv.weight, m.conv.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias]
-        off = heads[0].grad.data_ptr()
-        for t in heads:
-            if t.grad.data_ptr() != off:
-                raise RuntimeError("LNO: conv / fc1 / fc2 gradients are not contiguous in the flat buffer")
-            off += t.numel() * 4
-        if m.fc0.bias.grad.data_ptr() != m.fc0.weight.grad.data_ptr() + m.fc0.weight.numel() * 4:
+        if not grads_adjacent(m.conv.weight, m.conv.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias):
+            raise RuntimeError("LNO: conv / fc1 / fc2 gradients are not contiguous in the flat buffer")
+        if not grads_adjacent(m.fc0.weight, m.fc0.bias):
             raise RuntimeError("LNO: fc0 gradients are not contiguous in the flat buffer")
-        self.shape = (B, n1, n2, n3)
 
     def _desc(self, nb, ncp, nc2, pair_cp, pair_c2, conj_t=0, coef=(0, 0, 0), mult_conj=0, gscale=1.0):
         d = L.LnoTriDesc()
@@ -261,7 +232,7 @@ class LnoNative:
             self._wsegs.append((self.mu_re[d].data_ptr(), lp.weights_pole_real[d].grad.data_ptr(), self.mu_rows, cols))
             self._wsegs.append((self.mu_im[d].data_ptr(), lp.weights_pole_imag[d].grad.data_ptr(), self.mu_rows, cols))
 
-    def backward(self, gy: torch.Tensor) -> None:
+    def _backward(self, gy: torch.Tensor) -> None:
         """gy = dL/dy [B, n1, n2, n3, 1]; writes dL/d(parameter) into every parameter's `.grad` (views of flat_grad) and
         dL/dx into `self.gx` [B, N, data channels]."""
         m, lib = self.m, L.lib()
@@ -269,7 +240,6 @@ class LnoNative:
         Cw, N, Hd = m.width, self.N, m.hidden_features
         gy = gy.contiguous().view(B, N)
         st = _stream_ptr(self.y)
-        self._wsegs = []
         L.check(lib.ppsci_lno_head_bwd(B, N, Cw, Hd, L.ACT[m.activation], _p(self.x1n), _p(self.h), _p(m.conv.weight), _p(m.conv.bias),
                                        _p(m.fc1.weight), _p(m.fc1.bias), _p(m.fc2.weight), _p(gy), _p(self.g_x1n), _p(self.g_hc),
                                        _p(self.p_head), st))
@@ -286,16 +256,3 @@ class LnoNative:
         L.check(lib.ppsci_lno_lift_bwd(B, n1, n2, n3, self.fd, 1 if m.use_grid else 0, Cw, _p(self.x_in), _p(m.fc0.weight), _p(gh),
                                        _p(self.gx), _p(self.p_lift), st))
         self._wsegs.append((self.p_lift.data_ptr(), m.fc0.weight.grad.data_ptr(), self.rows, self.p_lift.shape[1]))
-        if not self.defer_wgrad_sums:
-            self._flush_wgrads()
-
-    def _flush_wgrads(self) -> None:
-        """ONE launch sums every partial-row matrix of the pass (ppsci_reduce_rows_multi, up to 16 segments per launch)."""
-        st = _stream_ptr(self.y)
-        for i0 in range(0, len(self._wsegs), 16):
-            batch = self._wsegs[i0:i0 + 16]
-            arr = (L.ReduceSeg * len(batch))()
-            for k, (src, dst, rows, cols) in enumerate(batch):
-                arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
-            L.check(L.lib().ppsci_reduce_rows_multi(len(batch), arr, st))
-        self._wsegs = []

@@ -1,5 +1,6 @@
 """Training engine of the operator-learning path (FNO): network forward + hand-written backward on this framework's
-kernels (fno_engine.FnoNative), the loss and its adjoint w.r.t. the network output from the loss object's own kernels
+kernels (the model's executor, native_executor.NativeExecutor), the loss and its adjoint w.r.t. the network output from the
+loss object's own kernels
 (loss.field: LpLoss / H1Loss / MSELoss on fields) -- gradients land in the model's flat buffer, one SUM all-reduce of that
 buffer per step and the fused Adam kernel on it: the same contract (`forward_backward`, `allreduce`, `grad`,
 `dp_reduce`) as `engine.Engine` for the PINN path.
@@ -64,7 +65,7 @@ class OperatorConstraint:
         return {k: f(data) for k, f in self.output_expr.items()}
 
     def forward_backward_native(self, native) -> None:
-        """Network forward + backward on the hand-written kernels (fno_engine.FnoNative).  dL/dy comes from the loss
+        """Network forward + backward on the hand-written kernels (native_executor.NativeExecutor).  dL/dy comes from the loss
         object itself when it has kernels for fields (`value_and_grad`: LpLoss / H1Loss / MSELoss on the raw network
         output); any other loss / output expression -- arbitrary Python on the network OUTPUT -- is differentiated by
         torch w.r.t. that one tensor (nothing of the network is on an autograd tape)."""
@@ -121,17 +122,8 @@ class OperatorEngine:
         from .engine import StepGraph
 
         self._step_graph = StepGraph(self.grad.is_cuda and os.environ.get("PPSCI_HIP_GRAPH", "1") != "0")
-        # forward and backward on this framework's own kernels, no autograd graph of the network (fno_engine.py)
-        from . import fno_engine, geofno_engine, lno_engine, uno_engine
-
-        whys = []
-        for executor in (fno_engine, uno_engine, lno_engine, geofno_engine):
-            whys.append(executor.supports(model))
-            if whys[-1] is None:
-                break
-        else:
-            raise NotImplementedError(f"operator engine: {whys[0]}")
-        # fno_engine.FnoNative / uno_engine.UnoNative / lno_engine.LnoNative / geofno_engine.Fno1dNative
+        # forward and backward on this framework's own kernels, no autograd graph of the network: the model's own executor
+        # (native_executor.NativeExecutor), which refuses a model its kernels do not cover with its own reason
         self.native = model.native()
 
     def _forward_backward_eager(self, constraints: List[OperatorConstraint]):
@@ -159,15 +151,14 @@ class OperatorEngine:
         finally:
             self.native.defer_wgrad_sums = False
         # (a replayed graph does not run Python: the segment list of the capturing / eager pass stays valid -- same buffers)
-        segs = list(self.native._wsegs) if self.native._wsegs else self._deferred_segs
+        segs = self.native.wgrad_segments or self._deferred_segs
         self._deferred_segs = segs
         return segs
 
     _deferred_segs = None
 
     def flush_deferred(self, segs) -> None:
-        self.native._wsegs = list(segs)
-        self.native._flush_wgrads()
+        self.native.flush_wgrads(segs)
 
     def allreduce(self):
         if self.world > 1:

@@ -187,10 +187,7 @@ class SpinnEngine:
         return self._segments(constraints)
 
     def flush_deferred(self, segs) -> None:
-        arr = (L.ReduceSeg * len(segs))()
-        for k, (src, dst, rows, cols) in enumerate(segs):
-            arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
-        L.check(L.lib().ppsci_reduce_rows_multi(len(segs), arr, _stream_ptr(self.grad)))
+        hp.reduce_rows_multi(segs, self.grad)
 
     def _forward_backward_eager(self, constraints: Sequence[SpinnConstraint], reduce: bool = True):
         P = self.model.branch_params
@@ -212,12 +209,7 @@ class SpinnEngine:
             segs.append((c0.gpart_all, self.grad[:3 * P], c0.gpart_all.shape[0], 3 * P))
         else:
             segs += [(c0.gpart[b], self.grad[b * P:(b + 1) * P], c0.gpart[b].shape[0], P) for b in range(3)]
-        for i0 in range(0, len(segs), 16):
-            batch = segs[i0:i0 + 16]
-            arr = (L.ReduceSeg * len(batch))()
-            for k, (src, dst, rows, cols) in enumerate(batch):
-                arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src.data_ptr(), dst.data_ptr(), rows, cols, 0
-            L.check(L.lib().ppsci_reduce_rows_multi(len(batch), arr, _stream_ptr(self.grad)))
+        hp.reduce_rows_multi([(src.data_ptr(), dst.data_ptr(), rows, cols) for src, dst, rows, cols in segs], self.grad)
         for c in constraints[1:]:
             if c.gjoint:
                 hp.reduce_rows(c.gpart_all, c.gpart_all.shape[0], 3 * P, self.grad[:3 * P], True)

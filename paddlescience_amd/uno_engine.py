@@ -1,7 +1,7 @@
 """Native forward + backward of ppsci.arch.UNONet (/root/reference/ppsci/arch/unonet.py:246-289): the FNO executor's kernels
 (fno_engine.FnoNative: MFMA 1x1 convolutions, raw hipFFT executions, the per-mode complex contraction, the fused
 bias + GroupNorm + skip block tail) plus the two operations of csrc/uno.hip that let a block change resolution, composed by hand
-in both directions -- no autograd graph, no library operator.
+in both directions -- no autograd graph, no library operator.  The contract is native_executor.NativeExecutor's.
 
 Per Fourier layer i, input grid (H, W) -> output grid (H2, W2) = round(size * uno_scalings[i]) (the last layer: the end-to-end
 grid, unonet.py:251-254, :273-274), channels Cin -> Cout:
@@ -88,24 +88,13 @@ class _Resampler:
 
 
 class UnoNative(FnoNative):
-    """Same contract as fno_engine.FnoNative (`forward`, `backward`, `generation`, deferred weight-gradient sums): the operator
-    engine, the solver's eval / predict paths and the HIP-graph capture of the step do not tell the two apart."""
+    """FnoNative's 1x1-convolution calls and weight-gradient partials (`_wgrad`) on this network's own buffers, in one stream."""
+
+    label, supports = "UNO", staticmethod(supports)
 
     def __init__(self, model):
-        why = supports(model)
-        if why is not None:
-            raise NotImplementedError(f"native UNO path: {why}")
-        self.m = model
-        self.shape = None
-        self._sets = {}
-        self.max_sets = 8
-        self.generation = 0
+        super().__init__(model)
         self.use_side = False
-        self._side = None
-
-    def _switch(self, B: int, H: int, W: int) -> None:
-        keep = ("m", "shape", "_sets", "max_sets", "generation", "use_side", "_side", "defer_wgrad_sums")
-        return self._switch_(B, H, W, keep)
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int, H0: int, W0: int) -> None:
@@ -137,7 +126,6 @@ class UnoNative(FnoNative):
         self.hw_out = (H0, W0) if self.padded else final
         P0, Pout = H0 * W0, self.hw_out[0] * self.hw_out[1]
         self.P0, self.Pout = P0, Pout
-        self.shape = (B, H0, W0)
         lift, proj = m.lifting.fcs, m.projection.fcs
         self.c_lift, self.c_proj = lift[0].out_channels, proj[0].out_channels
         Ch = m.hidden_channels
@@ -206,7 +194,7 @@ class UnoNative(FnoNative):
                  for e in self.blk) * 2
         self.gf = [torch.empty(nf, **f) for _ in range(3)]
         self._wbufs: List[torch.Tensor] = []
-        self._wcall, self._wsegs = 0, []
+        self._wcall = 0
 
     @staticmethod
     def _view(buf, *shape):
@@ -222,7 +210,7 @@ class UnoNative(FnoNative):
         m = self.m
         B, _, H0, W0 = x.shape
         if self.shape != (B, H0, W0):
-            self._switch(B, H0, W0)
+            self._switch((B, H0, W0))
         P0, Ch, nl = self.P0, m.hidden_channels, m.n_layers
         lift, proj = m.lifting.fcs, m.projection.fcs
         self.x_in = x.contiguous().view(B, m.in_channels, P0)
@@ -288,14 +276,14 @@ class UnoNative(FnoNative):
         return self.y.view(B, m.out_channels, *self.hw_out)
 
     # ------------------------------------------------------------------ backward
-    def backward(self, gy: torch.Tensor) -> None:
+    def _backward(self, gy: torch.Tensor) -> None:
         m = self.m
         B = self.shape[0]
         P0, Pout, Ch, nl = self.P0, self.Pout, m.hidden_channels, m.n_layers
         lift, proj = m.lifting.fcs, m.projection.fcs
         gy = gy.contiguous().view(B, m.out_channels, Pout)
         st = _stream_ptr(self.y)
-        self._wcall, self._wsegs = 0, []
+        self._wcall = 0
         V = self._view
         co = m.uno_out_channels[-1]
         # projection
@@ -395,5 +383,3 @@ class UnoNative(FnoNative):
         self._wgrad(B, self.c_lift, Ch, P0, self.a1, gx, lift[1].weight, lift[1].bias)
         _pw_conv(B, Ch, self.c_lift, P0, gx, lift[1].weight, gz1, zmul=self.z1, transpose=True)
         self._wgrad(B, m.in_channels, self.c_lift, P0, self.x_in, gz1, lift[0].weight, lift[0].bias)
-        if not self.defer_wgrad_sums:
-            self._flush_wgrads()
