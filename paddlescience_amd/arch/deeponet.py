@@ -31,12 +31,9 @@ import torch
 
 from .. import _lib as L
 from .. import hotpath as hp
-from ..device import get_device
 from . import activation as act_mod
-from .base import Arch
+from .layer_by_layer import FlatParamArch, LayerExec, LayerLayout, Stack, _p, _sp
 
-_p = hp._p
-_sp = hp._stream_ptr
 ONET_ACTS = ("tanh", "silu", "sigmoid", "sin", "cos", "gelu", "swish")
 
 
@@ -80,8 +77,8 @@ def _act_shapes(name: str, activation: str) -> List[Tuple[str, Tuple[int, ...]]]
     return [(f"{name}.beta", ())] if act_mod.get_activation(activation) == "swish" else []
 
 
-class _OnetBase(Arch):
-    """Shared parameter store, initialisation, state dict and numeric forward of the three operator nets."""
+class _OnetBase(FlatParamArch):
+    """Shapes, initialisation and executor inputs of the three operator nets."""
 
     def _setup(self, subs: List[_Sub], trunk: _Sub, trunk_act: str, act_params: List[Tuple[str, Tuple[int, ...]]],
                n_out: int, p: int, use_bias: bool):
@@ -104,33 +101,11 @@ class _OnetBase(Arch):
             shapes += s.shapes()
         shapes += trunk.shapes()
         shapes += _act_shapes("trunk_act", trunk_act) + act_params
-        self._shapes = shapes
-        self.reparam = False
-        self._bind_views(torch.zeros(max(1, sum(int(np.prod(s_)) for _, s_ in shapes)), dtype=torch.float32, device=get_device()))
-        self._frozen = False
+        self._store(shapes)
         self._init_parameters()
-        self._predict_exec: Dict[int, "OnetExec"] = {}
         self.layout = OnetLayout(self)
         # parameters the forward never reads (unused registered activations): no gradient, never moved by Adam
         self.unused = [n for n, _ in act_params]
-
-    # ---- parameters (arch/piratenet.py conventions)
-    def _bind_views(self, flat: torch.Tensor) -> None:
-        self.flat_params = self.kernel_params = flat
-        self._names, self._views, self._offsets = [], [], {}
-        off = 0
-        for name, shp in self._shapes:
-            n = int(np.prod(shp))
-            self._names.append(name)
-            self._views.append(flat[off:off + n].view(tuple(shp)))
-            self._offsets[name] = (off, n)
-            off += n
-        self._byname = dict(zip(self._names, self._views))
-
-    def rehome(self, flat: torch.Tensor, flat_grad=None, kernel=None) -> None:
-        assert flat.numel() == self.flat_params.numel()
-        flat.copy_(self.flat_params)
-        self._bind_views(flat)
 
     def _init_parameters(self):
         """nn.Linear: Xavier-uniform weight, zero bias (from numpy's global RNG, ppsci.utils.misc.set_random_seed);
@@ -146,81 +121,25 @@ class _OnetBase(Arch):
             else:
                 t[name].zero_()
 
-    def parameters(self) -> List[torch.Tensor]:
-        return list(self._views)
-
-    def named_parameters(self):
-        return list(zip(self._names, self._views))
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return dict(zip(self._names, self._views))
-
-    def set_state_dict(self, state):
-        missing = [n for n in self._names if n not in state]
-        unexpected = [n for n in state if n not in self._names]
-        for n, v in zip(self._names, self._views):
-            if n in state:
-                src = state[n]
-                src = torch.as_tensor(np.asarray(src.detach().cpu() if isinstance(src, torch.Tensor) else src), dtype=torch.float32)
-                if v.dim() == 0 and src.numel() == 1:  # a 0-d beta stored as [1]
-                    src = src.reshape(())
-                if tuple(src.shape) != tuple(v.shape):
-                    raise ValueError(f"shape mismatch for {n}: {tuple(src.shape)} vs {tuple(v.shape)}")
-                v.copy_(src)
-        return missing, unexpected
-
-    def materialize(self) -> torch.Tensor:
-        return self.flat_params
-
-    def pull_back(self, grad: torch.Tensor) -> torch.Tensor:
-        return grad
-
-    @property
-    def n_params(self) -> int:
-        return int(self.flat_params.numel())
-
     # ---- executors
     def make_exec(self, dirs: Sequence[Sequence[float]], n2: int, n: int, train: bool = True) -> "OnetExec":
         """Executor at 1 + len(dirs) + n2 streams: `dirs` are direction vectors over the TRUNK keys (derivatives along a
         branch key are outside this model)."""
-        return OnetExec(self, hp.StreamSpec([list(map(float, d)) for d in dirs], int(n2)), int(n), train=train)
+        return self._make_exec(hp.StreamSpec([list(map(float, d)) for d in dirs], int(n2)), int(n), train=train)
 
-    def _forward_numeric(self, x: Dict[str, object]) -> Dict[str, torch.Tensor]:
-        dev = self.flat_params.device
-        ins = {}
-        for k in self.input_keys:
-            if k not in x:
-                raise KeyError(f"input {k!r} of {type(self).__name__} is missing")
-            v = x[k]
-            if not isinstance(v, torch.Tensor):
-                v = torch.as_tensor(np.asarray(v), dtype=torch.float32)
-            ins[k] = v.to(device=dev, dtype=torch.float32).contiguous()
+    def _make_exec(self, spec, n, inputs=None, train=True, branch=None):
+        return OnetExec(self, spec, n, inputs, branch, train)
+
+    def _rows(self, ins: Dict[str, torch.Tensor]) -> int:
         n = int(ins[self.trunk_keys[0]].shape[0])
-        ex = self._predict_exec.get(n)
-        if ex is None:
-            if len(self._predict_exec) > 4:
-                self._predict_exec.clear()
-            ex = self._predict_exec[n] = OnetExec(self, hp.StreamSpec([], 0), n, train=False)
         for k in self.branch_keys:
             if int(ins[k].shape[0]) != n:
                 raise ValueError(f"branch key {k!r} has {int(ins[k].shape[0])} rows, the trunk keys {n}")
-        ex.set_inputs(ins)
-        U = torch.empty((self.n_out, n), dtype=torch.float32, device=dev)
-        ex.forward(self.flat_params, U)
-        return {k: U[i].view(n, 1) for i, k in enumerate(self.output_keys)}
+        return n
 
-    def forward(self, x: Dict[str, object]) -> Dict[str, object]:
+    def _check_transforms(self) -> None:
         if self._input_transform is not None or self._output_transform is not None:
             raise NotImplementedError(f"{type(self).__name__} with a registered input / output transform")
-        from ..graph import Sym
-
-        if any(isinstance(v, Sym) for v in x.values()):
-            for k in self.input_keys:  # a constraint's trace: the outputs are network nodes of the expression graph
-                v = x.get(k)
-                if not (isinstance(v, Sym) and v.kind == "in" and v.name == k):
-                    raise NotImplementedError(f"network input {k!r} must be the raw variable of the data dict")
-            return {k: Sym.net(self, i) for i, k in enumerate(self.output_keys)}
-        return self._forward_numeric(x)
 
 
 class DeepONet(_OnetBase):
@@ -302,26 +221,14 @@ class ChipDeepONets(_OnetBase):
                     use_bias)
 
 
-class OnetLayout:
-    """What compile / engine need to know about the operator net (the role hotpath.NetLayout plays for MLP): the engine
-    drives it as it drives PirateNet (engine.FusedConstraint, `is_pirate`).  `d_raw` counts the trunk keys only -- the
-    constraint's input columns and derivative directions; the branch keys reach the executor as [N, m] tensors bound by
-    compile.CompiledConstraint (`with_branch`), never through the epilogue program's input table."""
-
-    is_pirate = True
+class OnetLayout(LayerLayout):
+    """The layout of an operator net: `d_raw` counts the trunk keys only -- the constraint's input columns and derivative
+    directions; the branch keys reach the executor as [N, m] tensors bound by compile.CompiledConstraint (`with_branch`),
+    never through the epilogue program's input table."""
 
     def __init__(self, model: "_OnetBase", branch: Optional[Dict[str, torch.Tensor]] = None):
-        self.model, self.branch = model, branch
-        self.d_raw, self.d_out = len(model.trunk_keys), model.n_out
-        self.n_hidden, self.width = len(model.trunk.widths), max(model.trunk.widths)
-        self.embed, self.omega = None, None
-
-    @property
-    def n_params(self) -> int:
-        return int(self.model.flat_params.numel())
-
-    def desc(self, streams):
-        return None
+        super().__init__(model, len(model.trunk_keys), model.n_out, len(model.trunk.widths), max(model.trunk.widths))
+        self.branch = branch
 
     def with_branch(self, branch: Dict[str, torch.Tensor]) -> "OnetLayout":
         return OnetLayout(self.model, branch)
@@ -329,53 +236,26 @@ class OnetLayout:
     def make_exec(self, spec: hp.StreamSpec, n: int, inputs) -> "OnetExec":
         if self.branch is None:
             raise RuntimeError("the branch-key tensors of the constraint are not bound (compile.CompiledConstraint)")
-        return OnetExec(self.model, spec, n, inputs, self.branch)
+        return self.model._make_exec(spec, n, inputs, branch=self.branch)
 
 
-class _SubExec:
-    """Buffers of one sub-net at S streams."""
-
-    def __init__(self, sub: _Sub, S: int, NP: int, f32, train: bool):
-        self.sub, self.S, self.NP = sub, S, NP
-        blk = lambda c: torch.zeros((S, c, NP), **f32)  # noqa: E731
-        self.X = blk(sub.d_in)
-        self.Z = [blk(w) for w in sub.widths]
-        self.A = [blk(w) for w in sub.widths]
-        self.Y = blk(sub.d_out)  # last_fc output without its bias
-        if train:
-            cmax = max(sub.widths + [sub.d_out])
-            self.OB, self.ZB = torch.zeros(S * cmax * NP, **f32), torch.zeros(S * cmax * NP, **f32)
-            self.Ybar = blk(sub.d_out)
-
-
-class OnetExec:
-    """Buffers and launch sequence of one (operator net, stream set, batch size): forward(params, U) fills the row block
-    U [n_out * S, N] (pirate_out_fwd's layout); backward(params, Ubar, grad) overwrites `grad` [n_params] with
-    d loss / d (parameters)."""
+class OnetExec(LayerExec):
+    """Buffers and launch sequence of one (operator net, stream set, batch size): the branch nets are plain stacks at
+    S = 1, the trunk net one at all streams; forward fills U [n_out * S, N] (pirate_out_fwd's layout)."""
 
     def __init__(self, model: _OnetBase, spec: hp.StreamSpec, n: int, inputs: Optional[Sequence[torch.Tensor]] = None,
                  branch: Optional[Dict[str, torch.Tensor]] = None, train: bool = True):
         """inputs: the trunk keys' [N] device columns, read in place (engine.FusedConstraint's); branch: key -> [N, m]
         device tensor, packed at every forward (compile.CompiledConstraint's).  Without them the executor owns both and
         set_inputs fills them."""
-        if getattr(spec, "n3", 0) or getattr(spec, "n4", 0):
-            raise NotImplementedError(f"{type(model).__name__}: derivative order > 2")
         dt = len(model.trunk_keys)
-        for v in spec.dirs:
-            if len(v) != dt:
-                raise NotImplementedError(f"{type(model).__name__}: a derivative direction must span the trunk keys "
-                                          f"{model.trunk_keys} only (derivatives along a branch key are outside this model)")
-        self.model, self.spec, self.n = model, spec, int(n)
-        self.n1, self.n2 = len(spec.dirs), int(spec.n2)
-        self.S = 1 + self.n1 + self.n2
-        self.NP = (self.n + 15) // 16 * 16
-        dev = model.flat_params.device
-        self.f32 = dict(dtype=torch.float32, device=dev)
-        self.branches = [_SubExec(s, 1, self.NP, self.f32, train) for s in model.subs]
-        self.trunk = _SubExec(model.trunk, self.S, self.NP, self.f32, train)
-        self.trunk_in = list(inputs) if inputs is not None else [torch.zeros(self.n, **self.f32) for _ in model.trunk_keys]
-        if len(self.trunk_in) != dt or any(t.numel() != self.n for t in self.trunk_in):
-            raise ValueError(f"{type(model).__name__}: expected {dt} trunk columns of {self.n} values")
+        if any(len(v) != dt for v in spec.dirs):
+            raise NotImplementedError(f"{type(model).__name__}: a derivative direction must span the trunk keys "
+                                      f"{model.trunk_keys} only (derivatives along a branch key are outside this model)")
+        super().__init__(model, spec, n, inputs, type(model).__name__, model.trunk_keys, dt)  # no period / Fourier embedding
+        stack = lambda s, S: Stack(s.prefix + ".", s.d_in, s.widths, s.d_out, s.act, S, self.NP, self.f32)  # noqa: E731
+        self.branches = [(s, stack(s, 1)) for s in model.subs]
+        self.trunk = stack(model.trunk, self.S)
         self.branch_in: Dict[str, torch.Tensor] = {}
         for k, c in model.branch_cols.items():
             v = branch.get(k) if branch is not None else None
@@ -384,44 +264,30 @@ class OnetExec:
             elif tuple(v.shape) != (self.n, c) or not v.is_contiguous() or v.dtype != torch.float32:
                 raise ValueError(f"branch key {k!r}: expected a contiguous float32 [{self.n}, {c}] tensor")
             self.branch_in[k] = v
-        d = self.desc = L.PirateEmbedDesc()  # trunk inputs -> their streams (no period / Fourier embedding)
-        d.d_raw = d.d0 = dt
-        d.half, d.n1, d.n2 = 0, self.n1, self.n2
-        for q, v in enumerate(spec.dirs):
-            for j in range(dt):
-                d.dirs[q][j] = float(v[j])
-        d.N, d.NP = self.n, self.NP
-        self._in_ptrs = (C.c_void_p * dt)(*[t.data_ptr() for t in self.trunk_in])
         h = self.hdesc = L.OnetHeadDesc()
         h.J, h.p, h.n_out, h.n1, h.n2, h.act, h.N, h.NP = len(model.subs), model.p, model.n_out, self.n1, self.n2, \
             L.ACT[model.trunk_act], self.n, self.NP
-        self._B_ptrs = (C.c_void_p * L.ONET_MAX_J)(*[b.Y.data_ptr() for b in self.branches])
-        self._train = False
+        self._B_ptrs = (C.c_void_p * L.ONET_MAX_J)(*[b.Y.data_ptr() for _, b in self.branches])
         if train:
-            self._alloc_train()
+            self._begin_reverse()
 
     def _alloc_train(self):
         lib = L.lib()
         m, F = self.model, self.model.p * self.model.n_out
-        self._Bbar_ptrs = (C.c_void_p * L.ONET_MAX_J)(*[b.Ybar.data_ptr() for b in self.branches])
+        for st in [self.trunk] + [b for _, b in self.branches]:
+            st.alloc_train()
+        self._Bbar_ptrs = (C.c_void_p * L.ONET_MAX_J)(*[b.Ybar.data_ptr() for _, b in self.branches])
         self.hchunks = int(lib.ppsci_onet_head_chunks(self.NP))
         self.achunks = int(lib.ppsci_pirate_act_chunks(self.NP))
         self.p_tb = torch.zeros(self.hchunks * F, **self.f32)
         self.p_bb = torch.zeros(len(self.branches) * self.hchunks * F, **self.f32)
         self.p_beta = torch.zeros(F * self.hchunks, **self.f32)
         self.p_b = torch.zeros(self.hchunks * m.n_out, **self.f32)
-        self._pbufs: List[torch.Tensor] = []
-        self._train = True
 
     # ---- inputs
     def set_inputs(self, x: Dict[str, torch.Tensor]) -> None:
         """Copies a batch into the executor's input buffers. Trunk keys: [N] or [N, 1]; branch keys: [N, m] row-major."""
-        m = self.model
-        for dst, k in zip(self.trunk_in, m.trunk_keys):
-            v = x[k]
-            if v.numel() != self.n:
-                raise ValueError(f"trunk key {k!r}: expected {self.n} values, got shape {tuple(v.shape)}")
-            dst.copy_(v.reshape(-1))
+        super().set_inputs(x)
         for k, dst in self.branch_in.items():
             v = x[k]
             if v.shape[0] != self.n or v.numel() != dst.numel():
@@ -431,151 +297,62 @@ class OnetExec:
     def _pack(self) -> None:
         """Branch keys [N, m] -> the planar [m][NP] input block of their branch net (the concat of mlp.py:314)."""
         lib = L.lib()
-        for b in self.branches:
+        for s, b in self.branches:
             c0 = 0
-            for k in b.sub.keys:
+            for k in s.keys:
                 v = self.branch_in[k]
                 mcol = int(v.shape[1])
                 L.check(lib.ppsci_onet_pack(mcol, self.n, self.NP, _p(v), C.c_void_p(b.X.data_ptr() + 4 * c0 * self.NP),
                                             _sp(b.X)))
                 c0 += mcol
 
-    # ---- helpers
-    def _t(self, params, name):
-        off, n = self.model._offsets[name]
-        return params[off:off + n]
-
-    def _dense(self, S, x, W, fin, fout, out):
-        L.check(L.lib().ppsci_pw_conv(S, fin, fout, self.NP, _p(x), _p(W), 1, None, None, 0, _p(out), None, _sp(out)))
-
-    def _dense_t(self, S, gy, W, fin, fout, out):
-        L.check(L.lib().ppsci_pw_conv(S, fout, fin, self.NP, _p(gy), _p(W), 0, None, None, 0, _p(out), None, _sp(out)))
-
-    def _sub_fwd(self, se: _SubExec, params, n1: int, n2: int) -> None:
-        s, lib = se.sub, L.lib()
-        act = L.ACT[s.act]
-        y, fin = se.X, s.d_in
-        for i, w in enumerate(s.widths):
-            self._dense(se.S, y, self._t(params, f"{s.prefix}.linears.{i}.weight"), fin, w, se.Z[i])
-            beta = self._t(params, f"{s.prefix}.acts.{i}.beta") if s.act == "swish" else None
-            L.check(lib.ppsci_pirate_act_fwd(L.PIRATE_ACT, act, w, self.n, self.NP, n1, n2, _p(se.Z[i]),
-                                             _p(self._t(params, f"{s.prefix}.linears.{i}.bias")), None, None, None, _p(beta),
-                                             _p(se.A[i]), _sp(se.A[i])))
-            y, fin = se.A[i], w
-        self._dense(se.S, y, self._t(params, f"{s.prefix}.last_fc.weight"), fin, s.d_out, se.Y)
-
-    def _pbuf(self, n: int) -> torch.Tensor:
-        i = self._pcall
-        self._pcall += 1
-        if i == len(self._pbufs):
-            self._pbufs.append(torch.zeros(n, **self.f32))
-        assert self._pbufs[i].numel() >= n
-        return self._pbufs[i]
-
-    def _sum_later(self, part: torch.Tensor, rows: int, cols: int, dst: torch.Tensor) -> None:
-        self._psegs.append((part.data_ptr(), dst.data_ptr(), rows, cols))
-
-    def _flush_sums(self, like: torch.Tensor) -> None:
-        st = _sp(like)
-        for i0 in range(0, len(self._psegs), 16):
-            batch = self._psegs[i0:i0 + 16]
-            arr = (L.ReduceSeg * len(batch))()
-            for k, (src, dst, rows, cols) in enumerate(batch):
-                arr[k].partials, arr[k].out, arr[k].rows, arr[k].cols, arr[k].accumulate = src, dst, rows, cols, 0
-            L.check(L.lib().ppsci_reduce_rows_multi(len(batch), arr, st))
-        self._psegs = []
-
-    def _sub_bwd(self, se: _SubExec, params, grad, n1: int, n2: int) -> None:
-        """se.Ybar (adjoint of the last_fc output) -> weight / bias / beta gradients of the sub-net (no input adjoint)."""
-        s, lib, m = se.sub, L.lib(), self.model
-        act = L.ACT[s.act]
-        S, NP = se.S, self.NP
-        wchunks = int(lib.ppsci_pw_conv_wgrad_chunks(S, NP))
-
-        def wgrad(x, zbar, fin, fout, name):
-            part = self._pbuf(wchunks * fin * fout)
-            L.check(lib.ppsci_pw_conv_wgrad(S, fout, fin, NP, _p(zbar), _p(x), _p(part), None, _sp(part)))
-            ow, nw = m._offsets[name]
-            self._sum_later(part, wchunks, fin * fout, grad[ow:ow + nw])
-
-        nl = len(s.widths)
-        wl = s.widths[-1]
-        wgrad(se.A[-1], se.Ybar, wl, s.d_out, f"{s.prefix}.last_fc.weight")
-        ob = se.OB[: S * wl * NP]
-        self._dense_t(S, se.Ybar, self._t(params, f"{s.prefix}.last_fc.weight"), wl, s.d_out, ob)
-        for i in range(nl - 1, -1, -1):
-            w = s.widths[i]
-            yin, fin = (se.A[i - 1], s.widths[i - 1]) if i > 0 else (se.X, s.d_in)
-            zb = se.ZB[: S * w * NP]
-            pb = self._pbuf(self.achunks * w)
-            swish = s.act == "swish"
-            pbeta = self._pbuf(w * self.achunks) if swish else None
-            bname = f"{s.prefix}.linears.{i}.bias"
-            beta_name = f"{s.prefix}.acts.{i}.beta"
-            L.check(lib.ppsci_pirate_act_bwd(L.PIRATE_ACT, act, w, self.n, NP, n1, n2, _p(se.Z[i]), _p(self._t(params, bname)),
-                                             None, None, None, _p(self._t(params, beta_name)) if swish else None, _p(ob),
-                                             _p(zb), None, None, None, _p(pb), _p(pbeta), _sp(zb)))
-            o_, n_ = m._offsets[bname]
-            self._sum_later(pb, self.achunks, w, grad[o_:o_ + n_])
-            if swish:
-                o_, n_ = m._offsets[beta_name]
-                self._sum_later(pbeta, w * self.achunks, 1, grad[o_:o_ + n_])
-            wgrad(yin, zb, fin, w, f"{s.prefix}.linears.{i}.weight")
-            if i > 0:
-                ob = se.OB[: S * fin * NP]
-                self._dense_t(S, zb, self._t(params, f"{s.prefix}.linears.{i}.weight"), fin, w, ob)
-
     def _head_args(self, params):
-        m = self.model
-        bb = (C.c_void_p * L.ONET_MAX_J)(*[self._t(params, f"{b.sub.prefix}.last_fc.bias").data_ptr() for b in self.branches])
-        beta = self._t(params, "trunk_act.beta") if m.trunk_act == "swish" else None
+        bb = (C.c_void_p * L.ONET_MAX_J)(*[self._t(params, f"{s.prefix}.last_fc.bias").data_ptr() for s, _ in self.branches])
+        beta = self._t(params, "trunk_act.beta") if self.model.trunk_act == "swish" else None
         return bb, beta
 
     # ---- forward / reverse
     def forward(self, params: torch.Tensor, Urows: torch.Tensor, train: bool = True) -> None:
-        """Urows [n_out * S, N].  `train` is part of the executor contract engine.FusedConstraint calls (arch/piratenet.py);
-        the forward keeps the same buffers either way, because the reverse recomputes what it needs from them."""
+        """Urows [n_out * S, N].  The forward keeps the same buffers whether `train` or not, because the reverse recomputes
+        what it needs from them."""
         m, lib = self.model, L.lib()
         assert Urows.numel() == m.n_out * self.S * self.n
         self._pack()
-        for b in self.branches:
-            self._sub_fwd(b, params, 0, 0)
+        for _, b in self.branches:
+            self._stack_fwd(b, params, 0, 0)
         t = self.trunk
-        L.check(lib.ppsci_pirate_embed_fwd(C.byref(self.desc), self._in_ptrs, None, _p(t.X), _sp(t.X)))
-        self._sub_fwd(t, params, self.n1, self.n2)
+        self._embed_fwd(params, t.X)
+        self._stack_fwd(t, params, self.n1, self.n2)
         bb, beta = self._head_args(params)
         L.check(lib.ppsci_onet_head_fwd(C.byref(self.hdesc), _p(t.Y), _p(self._t(params, "trunk_net.last_fc.bias")),
                                         self._B_ptrs, bb, _p(beta), _p(self._t(params, "b")) if m.use_bias else None,
                                         _p(Urows), _sp(Urows)))
 
+    def _sub_bwd(self, st: Stack, params, grad, n1: int, n2: int) -> None:
+        """The sub-net's gradients from st.Ybar (no input adjoint)."""
+        self._stack_bwd(st, params, grad, n1, n2, int(L.lib().ppsci_pw_conv_wgrad_chunks(st.S, self.NP)), False)
+
     def backward(self, params: torch.Tensor, Ubar_rows: torch.Tensor, grad: torch.Tensor) -> None:
-        """`grad`: flat [n_params] slice of the gradient buffer, fully overwritten (the unused activation parameters get 0)."""
-        if not self._train:
-            raise RuntimeError("OnetExec built with train=False has no reverse buffers")
+        """The unused activation parameters get 0."""
+        self._begin_reverse()
         m, lib = self.model, L.lib()
         grad = grad.view(-1)
         assert Ubar_rows.numel() == m.n_out * self.S * self.n and grad.numel() == m.n_params
-        self._pcall, self._psegs = 0, []
         for name in m.unused:
-            o_, n_ = m._offsets[name]
-            grad[o_:o_ + n_].zero_()
+            self._t(grad, name).zero_()
         t, F = self.trunk, m.p * m.n_out
         bb, beta = self._head_args(params)
         L.check(lib.ppsci_onet_head_bwd(C.byref(self.hdesc), _p(t.Y), _p(self._t(params, "trunk_net.last_fc.bias")),
                                         self._B_ptrs, bb, _p(beta), _p(Ubar_rows), _p(t.Ybar), self._Bbar_ptrs, _p(self.p_tb),
                                         _p(self.p_bb), _p(self.p_beta), _p(self.p_b) if m.use_bias else None, _sp(t.Ybar)))
-        o_, n_ = m._offsets["trunk_net.last_fc.bias"]
-        self._sum_later(self.p_tb, self.hchunks, F, grad[o_:o_ + n_])
-        for j, b in enumerate(self.branches):
-            o_, n_ = m._offsets[f"{b.sub.prefix}.last_fc.bias"]
-            self._sum_later(self.p_bb[j * self.hchunks * F:], self.hchunks, F, grad[o_:o_ + n_])
+        self._sum(self.p_tb, self.hchunks, F, self._t(grad, "trunk_net.last_fc.bias"))
+        for j, (s, _) in enumerate(self.branches):
+            self._sum(self.p_bb[j * self.hchunks * F:], self.hchunks, F, self._t(grad, f"{s.prefix}.last_fc.bias"))
         if m.trunk_act == "swish":
-            o_, n_ = m._offsets["trunk_act.beta"]
-            self._sum_later(self.p_beta, F * self.hchunks, 1, grad[o_:o_ + n_])
+            self._sum(self.p_beta, F * self.hchunks, 1, self._t(grad, "trunk_act.beta"))
         if m.use_bias:
-            o_, n_ = m._offsets["b"]
-            self._sum_later(self.p_b, self.hchunks, m.n_out, grad[o_:o_ + n_])
+            self._sum(self.p_b, self.hchunks, m.n_out, self._t(grad, "b"))
         self._sub_bwd(t, params, grad, self.n1, self.n2)
-        for b in self.branches:
+        for _, b in self.branches:
             self._sub_bwd(b, params, grad, 0, 0)
         self._flush_sums(t.Ybar)

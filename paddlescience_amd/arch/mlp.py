@@ -71,7 +71,7 @@ class PeriodEmbedding:
 
 class _MLPMeta(type):
     """`ppsci.arch.MLP(...)` may hand back the layer-by-layer class (see MLP.__new__): such an object IS an MLP to user code
-    (`isinstance(model, ppsci.arch.MLP)`), although it shares its implementation with PirateNet."""
+    (`isinstance(model, ppsci.arch.MLP)`), although it shares its implementation with PirateNet (arch/layer_by_layer.StreamMLP)."""
 
     def __instancecheck__(cls, obj):
         if type.__instancecheck__(cls, obj):

@@ -16,10 +16,10 @@ class ModelList(Arch):
     def __init__(self, model_list: Tuple[Arch, ...]):
         super().__init__()
         model_list = tuple(model_list)
-        from .piratenet import PirateNet
+        from .layer_by_layer import StreamMLP  # PirateNet, ModifiedMLP (and LayerwiseMLP, which is an MLP to isinstance)
 
         for m in model_list:
-            if not isinstance(m, (MLP, PirateNet)):
+            if not isinstance(m, (MLP, StreamMLP)):
                 raise NotImplementedError("ModelList members must be ppsci.arch.MLP / PirateNet on the fused HIP path")
         keys: List[str] = []
         for m in model_list:  # the reference keeps a set; a stable order is needed for the kernels' input arrays

@@ -51,9 +51,9 @@ class FusedConstraint:
         self.nets = []
         row = 0
         for lay, off, spec, idx, pre in nets:
-            if getattr(lay, "is_pirate", False):
-                # PirateNet runs layer by layer (arch/piratenet.py): its executor stands in for taylor_fwd / taylor_bwd and
-                # delivers ONE gradient row in the trainable layout
+            if getattr(lay, "layer_by_layer", False):
+                # the network runs layer by layer (arch/layer_by_layer.py: PirateNet, ModifiedMLP, LayerwiseMLP, the DeepONets):
+                # its executor stands in for taylor_fwd / taylor_bwd and delivers ONE gradient row in the trainable layout
                 if pre is not None:
                     raise NotImplementedError("PirateNet with a registered input transform")
                 nr = lay.d_out * streams.S
