@@ -316,6 +316,10 @@ int ppsci_taylor_step_kind(const ppsci_mlp_desc* d, const ppsci_epilogue_desc* e
  * hidden matrices for the next step.  Both are read when a launch is PLANNED (workspace_bytes, _plan). */
 void ppsci_set_fused_step(int on);
 void ppsci_set_step_tail(int mode);
+/* test knob (process-global): how the one kernel behind a fused launch (step tail 3) is spread over the chip: 0 the default --
+ * four 256-thread workgroups per 16 x 16 block of a hidden matrix --, 1 one 1 024-thread workgroup per block.  Every column is
+ * summed in the same order by both, so all results are equal to the last bit (tests compare the two). */
+void ppsci_set_tail_split(int n);
 /* kind 2: residual programs made of loads, constants, +, -, *, negation and detach under MSE terms (every BASELINE PDE)
  * run pre-decoded (csrc/epilogue_vm.h epi_point_fast) instead of through the opcode interpreter; 0 forces the interpreter
  * (tests compare the two). */

@@ -173,6 +173,7 @@ _SYMBOLS = {
     "ppsci_taylor_step_kind": (C.c_int, [C.POINTER(MlpDesc), C.POINTER(EpilogueDesc), C.c_int64]),
     "ppsci_set_fused_step": (None, [C.c_int]),
     "ppsci_set_step_tail": (None, [C.c_int]),
+    "ppsci_set_tail_split": (None, [C.c_int]),
     "ppsci_set_fast_program": (None, [C.c_int]),
     "ppsci_taylor_step_run_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(AdamArgs), C.c_void_p, C.c_int]),
     "ppsci_taylor_step_plan_apply": (C.c_int, [C.c_void_p, C.POINTER(AdamArgs), C.c_void_p]),

@@ -51,19 +51,30 @@ __device__ __forceinline__ unsigned ppsci_cvt_pk_bf16(float a, float b) {
 // x minus the low / high bf16 of the packed pair h, as ONE instruction: v_dot2c_f32_bf16  x += h . (-1, 0)  resp.  h . (0, -1)
 // (the products are exact, and so is the sum: h is x rounded to 8 significand bits) -- instead of unpacking the bf16 into a
 // float (a shift or a mask) and subtracting: 7 instead of 9 VALU instructions per pair of values in ppsci_split.
-// The constant operands are kept out of the optimiser's sight (SGPRs): hipcc folds the packed pair (-1, 0) into the inline
+// The constant operands are kept out of the optimiser's sight (registers): hipcc folds the packed pair (-1, 0) into the inline
 // operand "-1.0", which the hardware reads as something else -- 65 456 of 65 536 results wrong on MI355X with literal
-// constants, 0 with register operands (tools/microbench/dot2_test.hip).
+// constants, 0 with register operands, scalar or vector (tools/microbench/dot2_test.hip).
+// Two forms, chosen per translation unit (DESIGN 4.2 has the resource table behind each choice):
+//   default: an SGPR behind a volatile barrier -- one s_mov_b32 per use, the two constants alternating in the same register
+//     (263 scalar moves and ~130 s_nop per tile in the fused tile kernel's loop);
+//   PPSCI_SPLIT_CONST_VGPR = 1 (defined by the unit's .hip file in front of its includes): a VGPR behind a plain barrier, which
+//     the optimiser may merge and hoist -- each constant is materialised once per kernel and costs two VGPRs, so only units whose
+//     kernels keep their scratch size and occupancy with it define it.
+#if defined(PPSCI_SPLIT_CONST_VGPR) && PPSCI_SPLIT_CONST_VGPR
+#define PPSCI_SPLIT_CONST_HIDE(k) asm("" : "+v"(k))
+#else
+#define PPSCI_SPLIT_CONST_HIDE(k) asm volatile("" : "+s"(k))
+#endif
 __device__ __forceinline__ float ppsci_bf16_sub_lo(unsigned h, float x) {
   typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
   unsigned k = 0x0000bf80u;  // (lo, hi) = (-1, 0)
-  asm volatile("" : "+s"(k));
+  PPSCI_SPLIT_CONST_HIDE(k);
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_, h), __builtin_bit_cast(bf16x2_, k), x, false);
 }
 __device__ __forceinline__ float ppsci_bf16_sub_hi(unsigned h, float x) {
   typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
   unsigned k = 0xbf800000u;  // (lo, hi) = (0, -1)
-  asm volatile("" : "+s"(k));
+  PPSCI_SPLIT_CONST_HIDE(k);
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_, h), __builtin_bit_cast(bf16x2_, k), x, false);
 }
 // v_mfma_f32_16x16x32_bf16: lane (g = l>>4, c = l&15) supplies A[i = c][k = 8g + j] and B[k = 8g + j][n = c], j = 0..7

@@ -31,6 +31,15 @@
 #ifndef PPSCI_FUSED_STATIC
 #define PPSCI_FUSED_STATIC 0  // 1 (taylor_fused_static_<act>.hip): this unit instantiates the kernels of compile-time residual programs
 #endif
+// Which instantiations keep the bias gradients as per-lane sums over the launch (LANE_BIAS in the kernel): those whose register
+// budget holds the L x 4 accumulators next to the L x S float4 of the stash without new scratch bytes -- read off the
+// compiler's resource table of every instantiation (DESIGN 4.2): L (S + 1) <= 20 for the tanh kernels of compile-time
+// programs (the primary config, 4 x 64 with S = 4, is at 20: 233 -> 253 VGPRs, no scratch), <= 12 for all others (the other
+// activations' derivative chains and the VM's parking of wave 0 leave less room).  The rest keep the per-tile sums.
+// -D'PPSCI_FUSED_LANE_BIAS(L,S,ACT,STATIC)=false': per-tile sums everywhere (A/B builds).
+#ifndef PPSCI_FUSED_LANE_BIAS
+#define PPSCI_FUSED_LANE_BIAS(L, S, ACT, STATIC) ((L) * ((S) + 1) <= (((STATIC) && (ACT) == PPSCI_ACT_TANH) ? 20 : 12))
+#endif
 #define PPSCI_FUSED_EPI_SCRATCH ((PPSCI_MAX_RES + PPSCI_MAX_EPARAM) * 16)  // epi_finale's LDS (floats)
 #define PPSCI_FUSED_MAX_IN 4  // raw inputs held in registers per lane (x, y, z, t); nets with more take the separate launches
 // x[j] for a runtime j out of the register array (a select chain: dynamic indexing would put the array into scratch)
@@ -106,6 +115,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   constexpr int W = NB;
   constexpr int L = LH;
   constexpr int NKP = NB / 2;
+  constexpr bool LANE_BIAS = PPSCI_FUSED_LANE_BIAS(LH, S, ACT, STATIC);
   static_assert(NB == 4, "one feature block per wave, both k-pairs of a layer's fragments held in registers");
   PPSCI_DYN_SMEM(smem);
   const FwdArgs& a = args.f;
@@ -200,6 +210,14 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   for (int l = 0; l < L - 1; ++l)
 #pragma unroll
     for (int ib = 0; ib < NB; ++ib) wacc[l][ib] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // LANE_BIAS: the bias gradients stay per-lane sums over all tiles of the workgroup (hb[0] of layer l behind its pointwise
+  // adjoint; the points of a ragged tile that do not exist carry zero seeds) and are summed over the 16 points ONCE, behind
+  // the tile loop -- instead of four dependent DPP adds per register and an LDS atomic per tile and layer, directly in front
+  // of the split and publish of zbar_l.  L x 4 registers; instantiations that have no room for them keep the per-tile sums.
+  f32x4 bacc[LANE_BIAS ? L : 1];
+#pragma unroll
+  for (int l = 0; l < (LANE_BIAS ? L : 1); ++l) bacc[l] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
 #ifdef PPSCI_FUSED_TIMERS
   if (tid < 16) ((unsigned*)ered)[tid] = 0u;
@@ -690,7 +708,9 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
           for (int s = 0; s < S; ++s) *(f32x4*)&ppsci_dbg_buf[(long long)blockIdx.x * PPSCI_DBG_STRIDE + (s * 256 + tid) * 4] = hb[s];
         }
 #endif
-        if (!PPSCI_ABL(2)) {
+        if constexpr (LANE_BIAS) {
+          if (!PPSCI_ABL(2)) bacc[l] += hb[0];
+        } else if (!PPSCI_ABL(2)) {
           f32x4 sb4;
 #pragma unroll
           for (int r = 0; r < 4; ++r) sb4[r] = ppsci_row_sum16_last(hb[0][r]);
@@ -965,6 +985,15 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
         if (args.t.external == 1) *q = wacc[l][ib];
         else ppsci_store_agent4(q, wacc[l][ib]);
       }
+  }
+  if constexpr (LANE_BIAS) {  // the per-lane bias sums -> gB (zero so far: nothing else writes it in this mode)
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+      f32x4 sb4;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sb4[r] = ppsci_row_sum16_last(bacc[l][r]);
+      if (c == 15) *(f32x4*)&gB[l * HP + 16 * wave + 4 * g] = sb4;
+    }
   }
   // ---- the workgroup's small accumulators -> its partial row (compact order of ppsci_small_params)
   __syncthreads();

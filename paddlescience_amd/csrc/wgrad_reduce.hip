@@ -241,6 +241,19 @@ __device__ __forceinline__ float wtail_adam(const ppsci_wred_extras& x, int idx,
   return pn;
 }
 
+// parameter index of column ci of the small tensors' rows; compact order of ppsci_small_params:
+// W0 | b_0 .. b_{L-1} | W_last | b_last (| activation parameters)
+__device__ __forceinline__ int wtail_small_index(const WTailArgs& a, int ci) {
+  const int H = a.H, L = a.L;
+  if (ci < a.d0 * H) return a.q.offW[0] + ci;
+  if (ci < (a.d0 + L) * H) {
+    const int lb = (ci - a.d0 * H) / H;
+    return a.q.offB[lb] + (ci - a.d0 * H - lb * H);
+  }
+  if (ci < (a.d0 + L + a.m) * H) return a.q.offW[L] + (ci - (a.d0 + L) * H);
+  return a.q.offB[L] + (ci - (a.d0 + L + a.m) * H);
+}
+
 __global__ void __launch_bounds__(1024) wgrad_tail_kernel(WTailArgs a) {
   __shared__ f32x4 red[16][64];
   __shared__ float tile[16][17];
@@ -326,15 +339,7 @@ __global__ void __launch_bounds__(1024) wgrad_tail_kernel(WTailArgs a) {
     float v = redf[lane];
 #pragma unroll
     for (int w = 1; w < 16; ++w) v += redf[w * 64 + lane];
-    // compact order of ppsci_small_params: W0 | b_0 .. b_{L-1} | W_last | b_last (| activation parameters)
-    const int H = a.H, L = a.L;
-    int idx;
-    if (ci < a.d0 * H) idx = a.q.offW[0] + ci;
-    else if (ci < (a.d0 + L) * H) {
-      const int lb = (ci - a.d0 * H) / H;
-      idx = a.q.offB[lb] + (ci - a.d0 * H - lb * H);
-    } else if (ci < (a.d0 + L + a.m) * H) idx = a.q.offW[L] + (ci - (a.d0 + L) * H);
-    else idx = a.q.offB[L] + (ci - (a.d0 + L + a.m) * H);
+    const int idx = wtail_small_index(a, ci);
     if (a.x.accumulate) v += a.row[idx];
     a.row[idx] = v;
     if (a.x.p != nullptr) wtail_adam(a.x, idx, v);
@@ -359,6 +364,140 @@ __global__ void __launch_bounds__(1024) wgrad_tail_kernel(WTailArgs a) {
   }
 }
 
+// The same sums on the whole chip (the default; ppsci_set_tail_split(1) selects the kernel above).  One 1 024-thread workgroup
+// per 16 x 16 block puts (L-1) NB^2 + ~9 workgroups on 256 CUs (57 at 4 x 64), each fetching its nrows x 1 KB alone.  A column's
+// sum depends on no other column, so the 64 float4 columns of a block go to FOUR workgroups of 256 threads -- workgroup
+// (block, g) owns the 16 lanes (g, c) of the block layout, thread (rg, c) = (tid >> 4, tid & 15) sums what thread (rg, lane) of
+// the kernel above sums, in the same four chains, and lane c of the first wave adds the 16 row groups in the same order: every
+// bit of every sum is that of the one-workgroup mapping.  The sub-block (rows in = 16 ib + 4g .. + 3, all 16 columns) holds what
+// its gradient, Adam update and fragments need: the forward fragment is the lane's own four values, and the backward
+// fragment's lanes (g', c' = 4g + i) read W[16 ib + 4g + i][16 ob + 4g' + r] -- rows of this sub-block only (a 4 x 17 LDS tile).
+// Small tensors: 16 columns per workgroup, same row groups and order.  Loss terms: the 16 waves of the kernel above are four
+// passes of this one's four waves.
+__global__ void __launch_bounds__(256) wgrad_tail_split_kernel(WTailArgs a) {
+  __shared__ f32x4 red[16][16];
+  __shared__ float tile[4][17];
+  const int tid = threadIdx.x, c = tid & 15, rg = tid >> 4;
+  const int b = blockIdx.x;
+  if (b < 4 * a.nblk) {
+    const int blk_l = b >> 2, g = b & 3, lane = 16 * g + c;
+    const long long stride4 = a.per_tile / 4;
+    const f32x4* src = (const f32x4*)a.rows_w + (long long)blk_l * 64 + lane;
+    f32x4 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int r0 = rg; r0 < a.nrows; r0 += 64) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {  // clamped index + select: the loads stay unconditional
+        const int r = r0 + 16 * u;
+        const f32x4 v = __builtin_nontemporal_load(&src[(long long)(r < a.nrows ? r : a.nrows - 1) * stride4]);
+        acc[u] += r < a.nrows ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    red[rg][c] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    __syncthreads();
+    if (tid >= 64) return;  // the first wave stays whole (ppsci_wave_sync below); its lanes 0 .. 15 own the sub-block
+    const bool own = tid < 16;
+    const int NB = a.q.NB, NKP = NB / 2;
+    const int l = blk_l / (NB * NB), blk = blk_l - l * NB * NB, ib = blk / NB, ob = blk - ib * NB;
+    f32x4 pn = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (own) {
+      f32x4 tot = red[0][c];
+#pragma unroll
+      for (int w = 1; w < 16; ++w) tot += red[w][c];
+      const int in0 = 16 * ib + 4 * g, out = 16 * ob + c;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (in0 + r < a.H && out < a.H) {
+          const int idx = a.q.offW[l + 1] + (in0 + r) * a.H + out;
+          float v = tot[r];
+          if (a.x.accumulate) v += a.row[idx];
+          a.row[idx] = v;
+          if (a.x.p != nullptr) pn[r] = wtail_adam(a.x, idx, v);
+        }
+      }
+    }
+    if (a.x.p == nullptr || a.frag == nullptr) return;
+    const long long per_layer = (long long)NB * NKP * 3 * 64;  // u32x4 units
+    if (own) {
+      // forward fragment: lane (g, c) of row block ob, k-block ib -- the thread's own four values
+      const ppsci_split4 sp = ppsci_split(pn);
+      u32x2* dst = (u32x2*)(a.frag + (long long)l * per_layer + (long long)((ob * NKP + (ib >> 1)) * 3) * 64 + lane) + (ib & 1);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) dst[(long long)p * 64 * 2] = sp.p[p];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tile[r][c] = pn[r];  // tile[i][j] = W[16 ib + 4g + i][16 ob + j]
+    }
+    ppsci_wave_sync();
+    if (own) {
+      // backward fragment: lane (gd, cd = 4g + i) of row block ib, k-block ob holds W[16 ib + cd][16 ob + 4 gd + r]
+      const int gd = c >> 2, i = c & 3, laned = 16 * gd + 4 * g + i;
+      f32x4 pt;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pt[r] = tile[i][4 * gd + r];
+      const ppsci_split4 sp = ppsci_split(pt);
+      u32x2* dst = (u32x2*)(a.frag + (long long)(a.L - 1 + l) * per_layer + (long long)((ib * NKP + (ob >> 1)) * 3) * 64 + laned) + (ob & 1);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) dst[(long long)p * 64 * 2] = sp.p[p];
+    }
+    return;
+  }
+  if (b < 4 * a.nblk + a.nsmall) {
+    float* redf = (float*)red;  // [16][16]
+    const int ci = (b - 4 * a.nblk) * 16 + c;
+    const int cc = ci < a.psmall ? ci : 0;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int r0 = rg; r0 < a.nrows; r0 += 64) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = r0 + 16 * u;
+        const float v = a.rows_s[(long long)(r < a.nrows ? r : a.nrows - 1) * a.psmall + cc];
+        acc[u] += r < a.nrows ? v : 0.f;
+      }
+    }
+    redf[rg * 16 + c] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    __syncthreads();
+    if (rg != 0 || ci >= a.psmall) return;
+    float v = redf[c];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) v += redf[w * 16 + c];
+    const int idx = wtail_small_index(a, ci);
+    if (a.x.accumulate) v += a.row[idx];
+    a.row[idx] = v;
+    if (a.x.p != nullptr) wtail_adam(a.x, idx, v);
+    return;
+  }
+  // the loss terms, in the order of the kernel above: its thread t = 64 w + lane sums rows t, t + 1024, ...; its wave w is wave
+  // w & 3 of this workgroup in pass w >> 2; then the 16 wave sums in order
+  float* redf = (float*)red;
+  const int lane = tid & 63, wv = tid >> 6;
+  for (int k = 0; k < a.x.n_res; ++k) {
+    for (int pass = 0; pass < 4; ++pass) {
+      float v = 0.f;
+#pragma unroll 4
+      for (int r = 256 * pass + tid; r < a.x.loss_nrows; r += 1024) v += a.x.loss_rows[(long long)r * a.loss_stride + k];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) redf[4 * pass + wv] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float s = redf[0];
+      for (int w = 1; w < 16; ++w) s += redf[w];
+      a.x.loss_out[k] = s;
+    }
+    __syncthreads();
+  }
+}
+
+#ifndef PPSCI_TAIL_SPLIT_DEFAULT
+#define PPSCI_TAIL_SPLIT_DEFAULT 0  // 1: a build whose default is the one-workgroup mapping (A/B measurements, tools/build_variant.py)
+#endif
+static int g_tail_split = PPSCI_TAIL_SPLIT_DEFAULT;
+extern "C" void ppsci_set_tail_split(int n) { g_tail_split = n == 1 ? 1 : (n == 0 ? PPSCI_TAIL_SPLIT_DEFAULT : 0); }
+
 int ppsci_wgrad_tail(const ppsci_mlp_desc& d, const ppsci_derived& q, int nrows, const float* rows_w, const float* rows_s,
                      float* row, const ppsci_wred_extras& x, void* frag, void* stream) {
   WTailArgs a;
@@ -375,11 +514,17 @@ int ppsci_wgrad_tail(const ppsci_mlp_desc& d, const ppsci_derived& q, int nrows,
   a.nrows = nrows;
   a.psmall = ppsci_small_params(d, q);
   a.nblk = (d.n_hidden - 1) * q.NB * q.NB;
-  a.nsmall = (a.psmall + 63) / 64;
   a.per_tile = (long long)(d.n_hidden - 1) * q.HP * q.HP;
   a.loss_stride = x.n_res;
   a.x = x;
-  PPSCI_LAUNCH(wgrad_tail_kernel, WTailArgs, a.nblk + a.nsmall + (x.loss_rows != nullptr ? 1 : 0), 1024, 0, stream, a);
+  const int nloss = x.loss_rows != nullptr ? 1 : 0;
+  if (g_tail_split == 1) {
+    a.nsmall = (a.psmall + 63) / 64;
+    PPSCI_LAUNCH(wgrad_tail_kernel, WTailArgs, a.nblk + a.nsmall + nloss, 1024, 0, stream, a);
+  } else {
+    a.nsmall = (a.psmall + 15) / 16;
+    PPSCI_LAUNCH(wgrad_tail_split_kernel, WTailArgs, 4 * a.nblk + a.nsmall + nloss, 256, 0, stream, a);
+  }
   if (PPSCI_LAST_LAUNCH_ERROR() != 0) {
     ppsci_set_error("wgrad_tail: launch failed");
     return PPSCI_E_LAUNCH;

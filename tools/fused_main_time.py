@@ -19,6 +19,7 @@ dev = torch.device("cuda", 0)
 flat = bench.bench_weights(2, [64] * 4, 1)
 X = np.random.default_rng(42).uniform([0, -1], [1, 1], (n, 2)).astype(np.float32)
 L.lib().ppsci_set_step_tail(tail)
+L.lib().ppsci_set_tail_split(int(os.environ.get("PPSCI_TAIL_SPLIT", "0")))  # 1: the tail kernel's one-workgroup-per-block mapping
 L.lib().ppsci_set_static_program(0 if os.environ.get("PPSCI_STATIC_PROGRAM", "1") == "0" else 1)
 lay = hp.NetLayout(2, 4, 64, 1, "tanh")
 xs = [torch.tensor(X[:, j].copy(), device=dev) for j in range(2)]
@@ -28,7 +29,8 @@ for _ in range(5):
     eng.train_step([cst], 1e-3)
 torch.cuda.synchronize()
 reps = int(os.environ.get("REPS", "40"))
-out = {"lib": os.path.basename(os.environ.get("PPSCI_HIP_LIB", "libppsci_hip.so")), "tail": tail, "points": n,
+out = {"lib": os.path.basename(os.environ.get("PPSCI_HIP_LIB", "libppsci_hip.so")), "tail": tail,
+       "tail_split": int(os.environ.get("PPSCI_TAIL_SPLIT", "0")), "points": n,
        "static_program": cst._step_plan.static_program,
        "step_us": round(bench.time_events(lambda: eng.train_step([cst], 1e-3), reps) * 1e6, 2),
        "main_us": round(bench.time_events(cst._step_plan.run_main, reps) * 1e6, 2)}
