@@ -817,6 +817,28 @@ int ppsci_modmlp_bwd_batch_parts(const ppsci_modmlp_desc* d, const ppsci_spinn_g
                                  const float* const* x, const float* scratch, const float* const* stash,
                                  float* const* grad_partials, int64_t partial_stride, void* stream);
 
+/* General residuals on a separable net (csrc/spinn_jet.inc): every derivative of per-axis order <= 2,
+ *   d^(a+b+c) u / dx^a dy^b dz^c (i,j,k) = sum_r fx^(a)[i,r] fy^(b)[j,r] fz^(c)[k,r],
+ * is a contraction of the streams F[3][n][R] the branch nets carry.  A constraint lists the order triples its residual program
+ * reads; the grid values go to ppsci_epilogue as its U rows and come back as Ubar.  Replaces SPINN.forward_tensor
+ * (/root/reference/ppsci/arch/spinn.py:140-167) under hvp_revrev / nested paddle.incubate.autograd.jvp
+ * (/root/reference/ppsci/equation/pde/helmholtz.py:27-41), one full-grid pass per derivative in the reference. */
+#define PPSCI_SPINN_MAX_JET 16 /* distinct order triples (of the 27) one constraint may read: each is a grid-sized row of U and of Ubar */
+typedef struct ppsci_spinn_jet_desc {
+  int32_t n[3];  /* points per axis, each >= 1 */
+  int32_t rank;  /* 1 .. 64 */
+  int32_t nq;    /* 1 .. PPSCI_SPINN_MAX_JET */
+  int32_t ord[PPSCI_SPINN_MAX_JET][3]; /* derivative order 0 .. 2 per axis of stream q */
+} ppsci_spinn_jet_desc;
+/* U[q][(i*ny + j)*nz + k] for every stream q (the SoA rows ppsci_epilogue reads).  spinn.py:140-167. */
+int ppsci_spinn_jet_fwd(const ppsci_spinn_jet_desc* d, const float* Fx, const float* Fy, const float* Fz, float* U, void* stream);
+/* Floats of scratch ppsci_spinn_jet_bwd needs (0 for an invalid descriptor). */
+int64_t ppsci_spinn_jet_scratch_floats(const ppsci_spinn_jet_desc* d);
+/* Fbar_a[d][i,r] = sum over the streams q with ord[q][a] == d of the contraction of Ubar[q] with the two other axes' factors; all
+ * three [3][n_a][R] blocks are fully overwritten.  Fixed summation order, no atomics.  The reverse of helmholtz.py:27-41. */
+int ppsci_spinn_jet_bwd(const ppsci_spinn_jet_desc* d, const float* Fx, const float* Fy, const float* Fz, const float* Ubar,
+                        float* scratch, float* Fbar_x, float* Fbar_y, float* Fbar_z, void* stream);
+
 /* ---- ppsci.arch.LNO, the Laplace neural operator (csrc/lno.inc, included by csrc/uno.hip) ---------------------------
  * Grid n[0] x n[1] x n[2] (N points), C channels, modes m[0] x m[1] x m[2] (M coefficients), pair = i * C + o.  Complex planes
  * are [plane][2][N] (real plane, imaginary plane), coefficient tensors [..][M][2]; the residues are the model's two real

@@ -67,6 +67,13 @@ class SpinnGridDesc(C.Structure):
                 ("czz", C.c_float), ("scale", C.c_float)]
 
 
+SPINN_MAX_JET = 16
+
+
+class SpinnJetDesc(C.Structure):  # ppsci_spinn_jet_desc
+    _fields_ = [("n", C.c_int32 * 3), ("rank", C.c_int32), ("nq", C.c_int32), ("ord", (C.c_int32 * 3) * SPINN_MAX_JET)]
+
+
 class PirateEmbedDesc(C.Structure):
     _fields_ = [("d_raw", C.c_int32), ("d0", C.c_int32), ("half", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
                 ("embed", C.c_int32 * MAX_IN), ("omega", C.c_float * MAX_IN), ("dirs", (C.c_float * MAX_IN) * MAX_DIRS),
@@ -323,6 +330,9 @@ _SYMBOLS = {
     "ppsci_spinn_grid_bwd_scratch_floats": (C.c_int64, [C.POINTER(SpinnGridDesc)]),
     "ppsci_spinn_grid_bwd": (C.c_int, [C.POINTER(SpinnGridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppsci_spinn_jet_fwd": (C.c_int, [C.POINTER(SpinnJetDesc)] + [C.c_void_p] * 5),
+    "ppsci_spinn_jet_scratch_floats": (C.c_int64, [C.POINTER(SpinnJetDesc)]),
+    "ppsci_spinn_jet_bwd": (C.c_int, [C.POINTER(SpinnJetDesc)] + [C.c_void_p] * 9),
     "ppsci_adam_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_int64, C.c_float, C.c_void_p]),
     "ppsci_optim_step": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

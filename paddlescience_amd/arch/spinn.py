@@ -7,7 +7,10 @@ buffer (branch 0, branch 1, branch 2; inside a branch in `parameters()` order). 
 re-initialised glorot-normal with zero bias like SPINN._init_weights (spinn.py:107-111).
 
 Traced use (expression compilation) returns `GridLinear` proxies: linear combinations of
-{u, u_xx, u_yy, u_zz}, which is what Helmholtz / Poisson-type residuals on a separable net need."""
+{u, u_xx, u_yy, u_zz}, which is what Helmholtz / Poisson-type residuals on a separable net need and what the
+four-coefficient grid kernels run.  Anything else -- u*u, u*u_x, sin(u), a mixed derivative, a coordinate factor --
+continues as an ordinary `Sym` graph over the per-axis derivative streams (orders 0..2 per axis) and runs on the
+general grid kernels of csrc/spinn_jet.inc with the epilogue VM between them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,37 +30,103 @@ from .base import Arch
 
 
 class GridLinear:
-    """cu*u + cxx*u_xx + cyy*u_yy + czz*u_zz on the tensor-product grid of a SPINN."""
+    """cu*u + cxx*u_xx + cyy*u_yy + czz*u_zz on the tensor-product grid of a SPINN.
+
+    A residual that stays of this form runs on the four-coefficient grid kernels.  Any other operation -- a product of two
+    forms, a function, meeting a traced expression -- continues with the ordinary expression graph of the same form (`sym`,
+    kept in the order the user wrote it), which is lowered for the general grid path (csrc/spinn_jet.inc)."""
 
     def __init__(self, model, cu=0.0, cxx=0.0, cyy=0.0, czz=0.0):
         self.model, self.c = model, np.array([cu, cxx, cyy, czz], dtype=np.float64)
+        # the same form as an expression graph, built in the order the user wrote it (what a promotion continues with)
+        keys = model.input_keys
+        self.sym = Sym.const(0.0)
+        for q, c in enumerate(self.c):
+            if c != 0.0:
+                self.sym = self.sym + float(c) * Sym.net(model, 0, () if q == 0 else (keys[q - 1],) * 2)
 
-    def _new(self, c):
-        g = GridLinear(self.model)
-        g.c = c
+    def _new(self, c, sym):
+        g = GridLinear.__new__(GridLinear)
+        g.model, g.c, g.sym = self.model, c, sym
         return g
+
+    def _as_sym(self) -> Sym:
+        return self.sym
+
+    @property
+    def shape(self):
+        return [-1, 1]
 
     def __add__(self, o):
         if isinstance(o, GridLinear):
-            return self._new(self.c + o.c)
+            return self._new(self.c + o.c, self.sym + o.sym)
         if isinstance(o, (int, float)) and o == 0:
             return self
-        raise NotImplementedError("only linear combinations of u, u_xx, u_yy, u_zz are fused for SPINN")
+        return self.sym + o
 
-    __radd__ = __add__
+    def __radd__(self, o):
+        if isinstance(o, (int, float)) and o == 0:
+            return self
+        return o + self.sym
 
     def __sub__(self, o):
-        return self + (-1.0) * o
+        if isinstance(o, GridLinear):
+            return self._new(self.c - o.c, self.sym - o.sym)
+        return self.sym - o
+
+    def __rsub__(self, o):
+        return o - self.sym
 
     def __mul__(self, k):
-        if not isinstance(k, (int, float, np.floating)):
-            raise NotImplementedError("SPINN residuals must be linear in u and its second derivatives")
-        return self._new(self.c * float(k))
+        if isinstance(k, (int, float, np.floating)):
+            return self._new(self.c * float(k), self.sym * float(k))
+        return self.sym * k
 
-    __rmul__ = __mul__
+    def __rmul__(self, k):
+        if isinstance(k, (int, float, np.floating)):
+            return self._new(self.c * float(k), float(k) * self.sym)
+        return k * self.sym
 
     def __neg__(self):
-        return self * -1.0
+        return self._new(-self.c, -self.sym)
+
+    def __truediv__(self, o):
+        return self.sym / o
+
+    def __rtruediv__(self, o):
+        return o / self.sym
+
+    def __pow__(self, o):
+        return self.sym ** o
+
+    def __rpow__(self, o):
+        return o ** self.sym
+
+    def __getattr__(self, name):  # u.sin(), u.tanh(), u.detach(), ...: the traced tensor surface of graph.Sym
+        if name.startswith("_") or not hasattr(Sym, name):
+            raise AttributeError(name)
+        return getattr(self.sym, name)
+
+
+class JetTable:
+    """The stream choice of one SPINN constraint for graph.lower: the distinct per-axis order triples (a, b, c) in {0,1,2}^3
+    its residual program reads, in order of first use.  Row q of the grid arrays U / Ubar is triple q."""
+
+    def __init__(self, model):
+        self.model, self.orders = model, []
+
+    def row(self, n: Sym) -> int:
+        keys = self.model.input_keys
+        t = tuple(n.dirs.count(k) for k in keys)
+        for k, o in zip(keys, t):
+            if o > 2:
+                raise NotImplementedError(f"derivative order {o} along axis {k!r} of a SPINN output: the branch nets carry orders 0..2")
+        if t not in self.orders:
+            if len(self.orders) >= L.SPINN_MAX_JET:
+                raise NotImplementedError(f"the residuals of one SPINN constraint read more than {L.SPINN_MAX_JET} distinct "
+                                          f"derivative streams (PPSCI_SPINN_MAX_JET); split the constraint")
+            self.orders.append(t)
+        return self.orders.index(t)
 
 
 class ModifiedMLPSpec:
@@ -85,12 +154,16 @@ class ModifiedMLPSpec:
 
 
 class SPINN(Arch):
+    max_axis_order = 2  # per-axis derivative order of the branch nets' streams (graph.diff)
+
     def __init__(self, input_keys: Tuple[str, ...], output_keys: Tuple[str, ...], r: int, num_layers: int,
                  hidden_size: Union[int, Tuple[int, ...]], activation: str = "tanh", skip_connection: bool = False,
                  weight_norm: bool = False, periods=None, fourier=None, random_weight=None):
         super().__init__()
         if len(input_keys) != 3 or len(output_keys) != 1:
-            raise NotImplementedError("the HIP SPINN path covers 3 input axes and one output (Helmholtz3D)")
+            raise NotImplementedError("the HIP SPINN path covers 3 input axes and one output: the reference's forward_tensor(x, y, z) "
+                                      "is fixed at three axes and its multi-output slicing returns the whole rank "
+                                      "(spinn.py:140-167)")
         if skip_connection or weight_norm or periods or fourier or random_weight or not isinstance(hidden_size, int):
             raise NotImplementedError("SPINN options beyond plain ModifiedMLP branches have no HIP kernel yet")
         self.input_keys, self.output_keys, self.r = tuple(input_keys), tuple(output_keys), r
@@ -171,3 +244,21 @@ class SPINN(Arch):
         c = [0.0, 0.0, 0.0, 0.0]
         c[1 + i] = 1.0
         return GridLinear(self, *c)
+
+    def derivative(self, *axis_keys: str):
+        """The derivative of the output along the given axes on the tensor-product grid, as a traced expression:
+        derivative("x") is u_x, derivative("x", "y") u_xy, derivative() u.  Per-axis order <= 2 (the branch nets' streams).
+        u and the pure second derivatives stay linear forms (GridLinear), so that a residual made of them alone keeps the
+        four-coefficient kernels."""
+        for k in axis_keys:
+            if k not in self.input_keys:
+                raise KeyError(f"SPINN.derivative: {k!r} is not an input axis {self.input_keys}")
+        for k in self.input_keys:
+            if axis_keys.count(k) > self.max_axis_order:
+                raise NotImplementedError(f"SPINN.derivative: order {axis_keys.count(k)} along axis {k!r}; the branch nets carry "
+                                          f"orders 0..{self.max_axis_order} per axis")
+        if len(axis_keys) == 0:
+            return GridLinear(self, cu=1.0)
+        if len(axis_keys) == 2 and axis_keys[0] == axis_keys[1]:
+            return self.second_derivative(axis_keys[0])
+        return Sym.net(self, 0, axis_keys)

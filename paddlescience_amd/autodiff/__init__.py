@@ -1,3 +1,3 @@
-from .ad import clear, hessian, jacobian  # noqa: F401
+from .ad import clear, hessian, jacobian, jvp  # noqa: F401
 
-__all__ = ["jacobian", "hessian", "clear"]
+__all__ = ["jacobian", "hessian", "jvp", "clear"]

@@ -1123,6 +1123,8 @@ __global__ void __launch_bounds__(GRID_BLOCK) spinn_fbar_sum_kernel(GridArgs a) 
   }
 }
 
+#include "spinn_jet.inc"  // the general (non-linear residual) contraction pair and its entry points
+
 // ------------------------------------------------------------------------------------ C ABI
 static int mod_check(const ppsci_modmlp_desc* d) {
   if (!d || d->width < 1 || d->width > SP_MAXH || d->n_hidden < 1 || d->n_hidden > PPSCI_MAX_HIDDEN || d->d_out < 1 ||

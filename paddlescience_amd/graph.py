@@ -469,6 +469,8 @@ def _lift(v) -> Sym:
         return Sym.const(float(v))
     if isinstance(v, np.ndarray) and v.size == 1:
         return Sym.const(float(v.reshape(-1)[0]))
+    if hasattr(v, "_as_sym"):  # arch.spinn.GridLinear meeting a traced expression: it continues as an ordinary graph
+        return v._as_sym()
     raise TypeError(f"cannot mix a traced expression with {type(v)}")
 
 
@@ -576,7 +578,13 @@ def diff(e: Sym, var: str) -> Sym:
                                       "derivatives run along the trunk keys only")
         if var not in net_raw_vars(e.model):
             return Sym.const(0.0)
-        if len(e.dirs) >= 4:
+        axis_max = getattr(e.model, "max_axis_order", None)
+        if axis_max is not None:  # separable nets: any mixed derivative, bounded per axis by the branch nets' streams
+            if e.dirs.count(var) >= axis_max:
+                raise NotImplementedError(
+                    f"derivative order {e.dirs.count(var) + 1} along axis {var!r} of the {type(e.model).__name__} output {e!r}: "
+                    f"the branch nets carry orders 0..{axis_max} per axis")
+        elif len(e.dirs) >= 4:
             raise NotImplementedError(
                 f"derivative order {len(e.dirs) + 1} of a network output ({e!r} w.r.t. {var}) is beyond the fused "
                 "HIP kernels (orders 0..4)")
@@ -687,14 +695,43 @@ class Lowered:
         self.nets: List[tuple] = []  # (model, StreamSpec, first U row, input indices) per network of the constraint
 
 
+def _check_separable(nodes, losses, jet) -> None:
+    """What a separable net's grid path (spinn_engine.SpinnJetConstraint) does not run, refused with the reason."""
+    what = type(jet.model).__name__
+    for n in nodes:
+        if n.kind == "param":
+            raise NotImplementedError(f"learnable equation parameter {n.name!r} in a {what} residual: the grid path has no "
+                                      "reduction for its gradient")
+        if n.kind == "reduce":
+            raise NotImplementedError(f"batch reduction {n!r} in a {what} residual: the grid is evaluated in one point-wise pass")
+        if n.kind == "couple":
+            raise NotImplementedError(f"batch coupling {n.name!r} in a {what} residual: the grid is evaluated in one point-wise pass")
+        if n.kind == "rows":
+            raise NotImplementedError(f"row slice {n!r} of a {what} residual: the output is a tensor-product grid, not a batch column")
+        if n.kind == "net" and n.model is not jet.model:
+            raise NotImplementedError(f"a second network in a {what} residual")
+    for ls in losses:
+        if ls.get("periodic"):
+            raise NotImplementedError(f"periodic loss on a {what} grid: its pairs are halves of a batch column")
+        if ls.get("causal"):
+            raise NotImplementedError(f"causal loss on a {what} grid: its windows are chunks of a batch column")
+        if ls.get("area"):
+            raise NotImplementedError(f"area column on a {what} grid")
+
+
 def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequence[str] = (),
-          n_global: Optional[int] = None) -> Lowered:
+          n_global: Optional[int] = None, jet=None) -> Lowered:
     """outputs: name -> traced expression.  losses: dicts with keys
          key (output name), label (aux name or None), weight (aux name or None), area (aux name or None), scale.
        Residual row k of the epilogue corresponds to losses[k]; `extra_outputs` are appended as
-       scale-0 residual rows so that eval / predict can read their values."""
+       scale-0 residual rows so that eval / predict can read their values.
+       jet: the stream choice of a separable net (arch.spinn.JetTable) instead of the Taylor kernels' direction set: U row q is
+       the q-th distinct per-axis order triple the program reads, in order of first use; the program is emitted as for any
+       other model."""
     roots = list(outputs.values())
     nodes = _walk(roots)
+    if jet is not None:
+        _check_separable(nodes, losses, jet)
     # batch reductions (Sym.mean / Sym.sum): reduction k is read from parameter slot k by the residual program
     reduces = [n for n in nodes if n.kind == "reduce"]
     if reduces:
@@ -733,7 +770,7 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
         order[d] = max(order.get(d, 0), k)
 
     for n in nodes:
-        if n.kind != "net" or not n.dirs:
+        if n.kind != "net" or not n.dirs or jet is not None:
             continue
         vs = sorted(set(n.dirs))
         k = len(n.dirs)
@@ -759,6 +796,9 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
     in_keys: List[str] = []  # union of the members' inputs: the constraint's input arrays
     for mm in model_list:
         in_keys += [k for k in net_raw_vars(mm) if k not in in_keys]
+
+    if jet is not None:
+        in_keys = list(jet.model.input_keys)
 
     def rank(d):  # variables in input order first, then the combined directions
         return (0, in_keys.index(d)) if isinstance(d, str) else (1, repr(d))
@@ -787,8 +827,8 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
     n1p, n2p, n3p, n4p = choice
     while len(dirs_vec) < n1p:  # padding directions are zero vectors: their streams vanish identically
         dirs_vec.append([0.0] * len(in_keys))
-    streams = hp.StreamSpec(dirs_vec, n2p, n3p, n4p)
-    S = streams.S
+    streams = hp.StreamSpec(dirs_vec, n2p, n3p, n4p) if jet is None else None
+    S = streams.S if jet is None else 1
     dir_index = {d: i for i, d in enumerate(dir_names)}
 
     # every member carries the same stream set; its direction vectors are expressed in ITS input order (a
@@ -798,7 +838,7 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
     row0: Dict[int, int] = {}
     rows = 0
     pre_nets: Dict[int, list] = {}  # id(model) -> per-feature stream expressions (input transform)
-    for mm in model_list:
+    for mm in ([] if jet is not None else model_list):
         feats = getattr(mm, "_traced_features", None)
         if feats:
             # a registered input transform: the network's inputs are functions phi_k of the raw variables; the
@@ -868,6 +908,8 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
                 val[id(n)] = prog.op(L.OP_SUB, val[id(n.args[0])], prog.ld_aux(aux_index(COUPLE_RHS_PREFIX + n.name)))
             elif n.kind == "const":
                 val[id(n)] = prog.const(n.value)
+            elif n.kind == "net" and jet is not None:
+                val[id(n)] = prog.ld_u(jet.row(n))
             elif n.kind == "net":
                 c = n.comp + row0[id(n.model)] // S  # rows of a member start at a multiple of S
                 if len(n.dirs) == 0:
@@ -913,6 +955,8 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
 
 
     emit(prog, nodes, val)
+    if jet is not None:
+        prog.n_streams = len(jet.orders)
 
     loss_keys = []
     couple_rows: Dict[str, tuple] = {}  # coupling name -> (residual row, weight aux)

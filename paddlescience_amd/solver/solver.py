@@ -202,26 +202,67 @@ class Solver:
         return dict(exprs)
 
     def _compile_spinn_constraint(self, name: str, cst):
-        """Separable nets: the expression must be linear in {u, u_xx, u_yy, u_zz} (arch.spinn.GridLinear)."""
+        """Separable nets.  One residual that is a linear form of {u, u_xx, u_yy, u_zz} without weights keeps the
+        four-coefficient grid kernels (arch.spinn.GridLinear -> SpinnConstraint); everything else -- several keys, weight grids,
+        non-linear residuals, first and mixed derivatives -- is lowered to an epilogue program over the derivative streams it
+        reads (SpinnJetConstraint).  PPSCI_SPINN_JET=1 sends a linear form down the general path too (A/B timing, tests)."""
         from ..arch.spinn import GridLinear
         from ..graph import Sym
         from ..spinn_engine import SpinnConstraint
 
         ds = getattr(cst.data_loader, "dataset", cst.data_loader)
-        if len(ds.label_keys) != 1:
-            raise NotImplementedError("one label key per SPINN constraint")
-        key = ds.label_keys[0]
+        label_keys = list(ds.label_keys)
+        if hasattr(ds, "weight_fn"):  # ContinuousNamedArrayDataset
+            w0 = ds.weight_fn(ds.input_fn()) if callable(ds.weight_fn) else None
+            weight_keys = list(w0.keys()) if w0 else []
+        else:
+            weight_keys = list((getattr(ds, "weight", None) or {}).keys())
         data = {k: Sym.input(k) for k in self.model.input_keys}
         data.update(self.model(data))
-        val = cst.output_expr[key](data) if key in cst.output_expr else data[key]
-        if not isinstance(val, GridLinear):
-            raise NotImplementedError(f"constraint {name}: expression {key!r} is not a linear form of the SPINN output")
+        vals = {k: (cst.output_expr[k](data) if k in cst.output_expr else data[k]) for k in label_keys}
+        autodiff.clear()
         loss = cst.loss
-        sc = SpinnConstraint(name, self.model, val.c, key, lambda total, k=key: loss.term_scale(k, total), self.device,
-                             self.world_size, self.rank)
+        key = label_keys[0] if label_keys else None
+        linear = (len(label_keys) == 1 and not weight_keys and isinstance(vals[key], GridLinear)
+                  and getattr(loss, "term_kind", 0) == 0 and os.environ.get("PPSCI_SPINN_JET", "0") != "1")
+        if linear:
+            sc = SpinnConstraint(name, self.model, vals[key].c, key, lambda total, k=key: loss.term_scale(k, total), self.device,
+                                 self.world_size, self.rank)
+        else:
+            sc = self._spinn_jet_constraint(name, vals, label_keys, weight_keys, loss)
         sc.batch_size = 0
-        sc.label_keys = [key]
+        sc.label_keys = label_keys
         return sc
+
+    def _spinn_jet_constraint(self, name, vals, label_keys, weight_keys, loss, extra_outputs=()):
+        """Lowers traced SPINN expressions with graph.lower (the program builder of every other model) on a stream table of
+        per-axis derivative orders."""
+        from .. import _lib, graph
+        from ..arch.spinn import JetTable
+        from ..compile import LABEL_PREFIX, WEIGHT_PREFIX
+        from ..spinn_engine import SpinnJetConstraint
+
+        if len(label_keys) + len(extra_outputs) > _lib.MAX_RES:
+            raise NotImplementedError(f"constraint {name}: {len(label_keys) + len(extra_outputs)} expression keys; one epilogue "
+                                      f"program holds {_lib.MAX_RES} (PPSCI_MAX_RES)")
+        if weight_keys and hasattr(loss, "batch_weight"):
+            raise NotImplementedError(f"constraint {name}: {type(loss).__name__} with weight grids on a SPINN grid: the reference "
+                                      "broadcasts its per-sample errors against the weight column of a batch, which a grid has not")
+        outputs = {}
+        for k, v in vals.items():
+            v = v._as_sym() if hasattr(v, "_as_sym") else v
+            outputs[k] = v if isinstance(v, graph.Sym) else graph._lift(v)
+        losses = [dict(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None, area=None,
+                       scale=1.0, kind=getattr(loss, "term_kind", 0), causal=(k if getattr(loss, "causal", None) else None),
+                       periodic=bool(getattr(loss, "periodic", False))) for k in label_keys]
+        jet = JetTable(self.model)
+        try:
+            low = graph.lower(outputs, losses, extra_outputs, jet=jet)
+        except NotImplementedError as e:
+            raise NotImplementedError(f"constraint {name}: {e}") from None
+        return SpinnJetConstraint(name, self.model, low, jet, label_keys,
+                                  [(lambda total, k=k: loss.term_scale(k, total)) for k in label_keys], self.device,
+                                  self.world_size, self.rank)
 
     def _compile_constraint(self, name: str, cst) -> CompiledConstraint:
         if self._is_spinn:
@@ -331,7 +372,7 @@ class Solver:
                     if not self._static[name]:
                         inp, lab, w = next(self.constraint[name].data_iter)
                         if self._is_spinn:
-                            cc.bind(inp, lab)
+                            cc.bind(inp, lab, w)
                         else:
                             cc.bind(inp, lab, self._shard_weights(name, self.constraint[name], lab, w))
                 reader_cost = time.perf_counter() - reader_tic
@@ -582,7 +623,7 @@ class Solver:
                 vals = cc.losses()  # keys are whatever the loss returns (FunctionalLoss), not the label keys
                 keys = list(vals.keys())
             else:
-                vals = {cc.label_key: cc.loss()} if self._is_spinn else cc.fused.losses()
+                vals = cc.losses() if self._is_spinn else cc.fused.losses()
                 keys = cc.label_keys
                 if getattr(self.loss_aggregator, "per_loss_grad", False) and hasattr(cc, "_base_scales"):
                     # the kernels applied the aggregator's weights through the residual scales: report raw terms
@@ -735,9 +776,25 @@ class Solver:
             pred = {k: torch.cat(v, 0) for k, v in res.items()}
             return {k: v.cpu().numpy() for k, v in pred.items()} if return_numpy else pred
         if self._is_spinn:  # tensor-product grid of the three coordinate vectors (helmholtz3d.py:205-213)
-            if expr_dict is not None:
-                raise NotImplementedError("expr_dict with a SPINN model")
             out = self.model(input_dict)
+            if expr_dict is not None:
+                # the expressions on the same grid through the general path: forward sweep, stream contraction and the epilogue's
+                # residual rows (no adjoint), as [nx,ny,nz,1] arrays next to the model outputs
+                from ..graph import Sym
+
+                ck = (id(expr_dict), "spinn")
+                if ck not in self._predict_cache:
+                    data = {k: Sym.input(k) for k in self.model.input_keys}
+                    data.update(self.model(data))
+                    vals = {k: f(data) for k, f in expr_dict.items()}
+                    autodiff.clear()
+                    # (the dict is kept with its constraint: its id stays unique for as long as the cache entry lives)
+                    self._predict_cache[ck] = (self._spinn_jet_constraint("predict", vals, [], [], None, tuple(expr_dict)), expr_dict)
+                cc = self._predict_cache[ck][0]
+                cc.world = 1  # every rank evaluates the grid it is given
+                cc.bind({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in input_dict.items()}, {})
+                cc.forward(False, False, want_resid=True)
+                out = dict(out, **{k: v.clone() for k, v in cc.values().items()})
             return {k: v.detach().cpu().numpy() for k, v in out.items()} if return_numpy else out
         n = len(next(iter(input_dict.values())))
         batch_size = n if batch_size is None else batch_size

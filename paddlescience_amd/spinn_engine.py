@@ -66,7 +66,19 @@ class SpinnConstraint:
         self.bscratch = torch.zeros(max(4, int(L.lib().ppsci_spinn_grid_bwd_scratch_floats(C.byref(self.desc)))), **f32)
         self.loss_term = torch.zeros(1, **f32)
 
-    def bind(self, input: Dict[str, np.ndarray], label: Dict[str, np.ndarray]):
+    lcols = 1  # columns of `lpart` / entries of `loss_term` (one loss key)
+
+    @property
+    def scale_key(self):  # what a captured step holds by value besides the buffers
+        return float(self.desc.scale)
+
+    def losses(self) -> Dict[str, float]:
+        return {self.label_key: self.loss()}
+
+    def bind(self, input: Dict[str, np.ndarray], label: Dict[str, np.ndarray], weight: Optional[Dict[str, np.ndarray]] = None):
+        if weight:
+            raise NotImplementedError("per-point weights on the four-coefficient SPINN path (the solver compiles a weighted "
+                                      "constraint for the general path)")
         keys = self.model.input_keys
         arrs = [np.asarray(input[k], dtype=np.float32).reshape(-1) for k in keys]
         lab = np.asarray(label[self.label_key], dtype=np.float32)
@@ -152,6 +164,200 @@ class SpinnConstraint:
         return float(self.loss_term.cpu()[0])
 
 
+class SpinnJetConstraint:
+    """A constraint whose residuals are NOT a linear form of {u, u_xx, u_yy, u_zz}: per step
+      3 x modmlp_fwd  ->  spinn_jet_fwd (the derivative streams the program reads, as rows U[nq][nx*ny*nz])
+                      ->  ppsci_epilogue over the grid points (residual program, loss terms, adjoint rows Ubar)
+                      ->  spinn_jet_bwd  ->  3 x modmlp_bwd.
+    `low` is the graph.Lowered of the traced expressions (graph.lower with the arch.spinn.JetTable `jet` as its stream choice).
+    Same attributes as SpinnConstraint, so that SpinnEngine and the solver treat both alike; `lpart` has one column per loss
+    key and `loss_term` one entry per key."""
+
+    def __init__(self, name: str, model, low, jet, label_keys: Sequence[str], scale_fns, device, world: int = 1, rank: int = 0):
+        from .compile import LABEL_PREFIX, WEIGHT_PREFIX
+
+        self.name, self.model, self.low, self.jet = name, model, low, jet
+        self.label_keys = list(label_keys)
+        self.label_key = self.label_keys[0] if self.label_keys else None
+        self.scale_fns = list(scale_fns)  # per loss term: total_points -> loss scale
+        self.device, self.world, self.rank = device, world, rank
+        self.program = low.program
+        if not jet.orders:
+            raise NotImplementedError(f"constraint {name}: the expressions do not read the network")
+        # what each aux row of the program is: ("label" | "weight", key)
+        self.aux_src = []
+        for a in low.aux_names:
+            if a.startswith(LABEL_PREFIX):
+                self.aux_src.append(("label", a[len(LABEL_PREFIX):]))
+            elif a.startswith(WEIGHT_PREFIX):
+                self.aux_src.append(("weight", a[len(WEIGHT_PREFIX):]))
+            else:
+                raise NotImplementedError(f"constraint {name}: the expression reads {a!r}, which is neither an input axis of the "
+                                          "SPINN nor a label / weight grid")
+        self.in_used = sorted({a for op, a, _, _ in self.program.instrs if op == L.OP_LD_IN})
+        self.shape = None
+        self._version = 0
+        self._scales = None
+        self.edesc = None
+
+    @property
+    def lcols(self) -> int:
+        return len(self.program.res)
+
+    @property
+    def scale_key(self):
+        return self._scales
+
+    def _alloc(self, shape):
+        m, dev = self.model, self.device
+        self.shape = tuple(shape)
+        self._version += 1
+        self._last_ids, self._uploaded = {}, {}
+        R, P = m.spec.R, m.branch_params
+        f32 = dict(dtype=torch.float32, device=dev)
+        total = shape[0] * shape[1] * shape[2]
+        nq = len(self.jet.orders)
+        self.x = [torch.zeros(n, **f32) for n in shape]
+        self.F = [torch.zeros((3, n, R), **f32) for n in shape]
+        self.Fbar = [torch.zeros((3, n, R), **f32) for n in shape]
+        self.stash = [torch.zeros(int(L.lib().ppsci_modmlp_stash_floats(C.byref(m.spec.desc), n)), **f32) for n in shape]
+        grows = [int(L.lib().ppsci_modmlp_bwd_rows(C.byref(m.spec.desc), n)) for n in shape]
+        self.gjoint = len(set(shape)) == 1
+        if self.gjoint:
+            self.gpart_all = torch.zeros((grows[0], 3 * P), **f32)
+            self.gpart = [self.gpart_all.view(-1)[b * P:] for b in range(3)]
+        else:
+            self.gpart = [torch.zeros((r, P), **f32) for r in grows]
+        self.jdesc = L.SpinnJetDesc()
+        self.jdesc.n[0], self.jdesc.n[1], self.jdesc.n[2] = shape
+        self.jdesc.rank, self.jdesc.nq = R, nq
+        for q, t in enumerate(self.jet.orders):
+            for a in range(3):
+                self.jdesc.ord[q][a] = t[a]
+        self.U = torch.zeros((nq, total), **f32)
+        self.Ubar = torch.zeros((nq, total), **f32)
+        # the inputs the program loads, expanded to the grid; the others are never read (any valid pointer)
+        self.xgrid = {j: torch.zeros(total, **f32) for j in self.in_used}
+        self.aux = [torch.zeros(total, **f32) for _ in self.aux_src]
+        self.lrows = hp.epilogue_partial_rows(total)
+        self.lpart = torch.zeros((self.lrows, max(1, self.lcols)), **f32)
+        self.loss_term = torch.zeros(max(1, self.lcols), **f32)
+        self.resid = None  # [n_res][total], allocated by predict-style use (values())
+        self.bscratch = torch.zeros(max(4, int(L.lib().ppsci_spinn_jet_scratch_floats(C.byref(self.jdesc)))), **f32)
+
+    @staticmethod
+    def _grid_array(a, gshape, what):
+        """A label / weight as a grid: an [nx,ny,nz(,1)] array or a scalar."""
+        a = np.asarray(a, dtype=np.float32)
+        if a.size == 1:
+            return np.broadcast_to(a.reshape(()), gshape)
+        if a.size != gshape[0] * gshape[1] * gshape[2]:
+            raise ValueError(f"{what}: {a.shape} is neither a scalar nor a grid of {gshape} points")
+        return a.reshape(gshape)
+
+    def bind(self, input: Dict[str, np.ndarray], label: Dict[str, np.ndarray], weight: Optional[Dict[str, np.ndarray]] = None):
+        keys = self.model.input_keys
+        arrs = [np.asarray(input[k], dtype=np.float32).reshape(-1) for k in keys]
+        gshape = tuple(a.shape[0] for a in arrs)
+        srcs = {"label": label or {}, "weight": weight or {}}
+        grids = []
+        for kind, k in self.aux_src:
+            if k not in srcs[kind]:
+                raise KeyError(f"constraint {self.name}: no {kind} for {k!r}")
+            grids.append(self._grid_array(srcs[kind][k], gshape, f"{kind} {k!r}"))
+        rep = 1.0
+        if self.world > 1:  # the rank-strided slab rule of SpinnConstraint.bind, applied to the label AND weight grids
+            ax = next((i for i, n in enumerate(gshape) if n >= self.world), None)
+            if ax is None:
+                rep = 1.0 / self.world
+            else:
+                arrs[ax] = arrs[ax][self.rank::self.world]
+                idx = [slice(None)] * 3
+                idx[ax] = slice(self.rank, None, self.world)
+                grids = [g[tuple(idx)] for g in grids]
+        shape = tuple(a.shape[0] for a in arrs)
+        if self.shape != shape:
+            self._alloc(shape)
+
+        def _fp(a):
+            f = np.asarray(a).reshape(-1)
+            n = f.shape[0]
+            return (id(a), n, float(f[0]), float(f[n // 2]), float(f[n - 1])) if n else (id(a), 0)
+
+        def upload(slot, src, make, dst):
+            """`make()` -> `dst` unless `src` is unchanged since the last upload into `slot` (SpinnConstraint.bind's rule)."""
+            fp = _fp(src)
+            if fp == self._last_ids.get(slot):
+                return False
+            self._last_ids[slot] = fp
+            val = np.ascontiguousarray(make(), dtype=np.float32).reshape(-1)
+            old = self._uploaded.get(slot)
+            if old is not None and old.shape == val.shape and np.array_equal(old, val):
+                return False
+            self._uploaded[slot] = val.copy()
+            dst.copy_(torch.from_numpy(val))
+            return True
+
+        for j, k in enumerate(keys):
+            if upload(("x", j), input[k], lambda j=j: arrs[j], self.x[j]) or ("g", j) not in self._last_ids:
+                if j in self.xgrid:  # coordinate j as a value of the program: once per bind of new coordinates
+                    self._last_ids[("g", j)] = True
+                    view = [1, 1, 1]
+                    view[j] = shape[j]
+                    self.xgrid[j].copy_(self.x[j].view(*view).expand(*shape).reshape(-1))
+        for i, ((kind, k), g) in enumerate(zip(self.aux_src, grids)):
+            upload(("aux", i), srcs[kind][k], lambda g=g: g, self.aux[i])
+        total_global = gshape[0] * gshape[1] * gshape[2]
+        scales = tuple(float(f(total_global)) * rep for f in self.scale_fns)
+        if scales != self._scales or self.edesc is None:
+            self._scales = scales
+            res = self.program.res
+            for k, sc in enumerate(scales):
+                res[k] = res[k][:4] + (sc,) + res[k][5:]
+            self.edesc = self.program.build()
+
+    def _epilogue_args(self):
+        any_x = self.x[0]
+        inputs = [self.xgrid.get(j, any_x) for j in range(len(self.model.input_keys))]
+        return inputs
+
+    def forward(self, train: bool, reduce_loss: bool = True, want_resid: bool = False):
+        m, lib = self.model, L.lib()
+        vp = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])  # noqa: E731
+        st = _stream_ptr(self.x[0])
+        L.check(lib.ppsci_modmlp_fwd_batch(C.byref(m.spec.desc), 3, vp([m.branch(b) for b in range(3)]),
+                                           (C.c_int64 * 3)(*[t.numel() for t in self.x]), vp(self.x), vp(self.F),
+                                           vp(self.stash) if train else None, st))
+        L.check(lib.ppsci_spinn_jet_fwd(C.byref(self.jdesc), _p(self.F[0]), _p(self.F[1]), _p(self.F[2]), _p(self.U), st))
+        if want_resid and self.resid is None:
+            self.resid = torch.zeros((max(1, self.lcols), self.U.shape[1]), dtype=torch.float32, device=self.device)
+        hp.epilogue(self.edesc, self.U.shape[1], self._epilogue_args(), self.U, self.aux, self.resid if want_resid else None,
+                    self.Ubar if train else None, self.lpart)
+        if reduce_loss:
+            hp.reduce_rows(self.lpart, self.lrows, self.lcols, self.loss_term, False)
+
+    def backward(self):
+        m, lib = self.model, L.lib()
+        vp = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])  # noqa: E731
+        st = _stream_ptr(self.x[0])
+        L.check(lib.ppsci_spinn_jet_bwd(C.byref(self.jdesc), _p(self.F[0]), _p(self.F[1]), _p(self.F[2]), _p(self.Ubar),
+                                        _p(self.bscratch), _p(self.Fbar[0]), _p(self.Fbar[1]), _p(self.Fbar[2]), st))
+        L.check(lib.ppsci_modmlp_bwd_batch(C.byref(m.spec.desc), 3, vp([m.branch(b) for b in range(3)]),
+                                           (C.c_int64 * 3)(*[t.numel() for t in self.x]), vp(self.x), vp(self.Fbar),
+                                           vp(self.stash), vp(self.gpart), 3 * m.branch_params if self.gjoint else 0, st))
+
+    def losses(self) -> Dict[str, float]:
+        t = self.loss_term.cpu()
+        return {k: float(t[i]) for i, k in enumerate(self.label_keys)}
+
+    def loss(self) -> float:
+        return float(sum(self.losses().values()))
+
+    def values(self) -> Dict[str, torch.Tensor]:
+        """The residual rows of the last forward(want_resid=True), as [nx,ny,nz,1] grids per output name."""
+        return {k: self.resid[i].view(*self.shape, 1) for i, k in enumerate(self.low.loss_keys)}
+
+
 class SpinnEngine:
     def __init__(self, model):
         self.model = model
@@ -167,7 +373,7 @@ class SpinnEngine:
         rows and the gradient rows of the three branch nets."""
         P = self.model.branch_params
         c0 = constraints[0]
-        segs = [(c0.lpart.data_ptr(), c0.loss_term.data_ptr(), c0.lrows, 1)]
+        segs = [(c0.lpart.data_ptr(), c0.loss_term.data_ptr(), c0.lrows, c0.lcols)]
         if c0.gjoint:
             segs.append((c0.gpart_all.data_ptr(), self.grad.data_ptr(), c0.gpart_all.shape[0], 3 * P))
         else:
@@ -182,7 +388,7 @@ class SpinnEngine:
         if len(constraints) != 1:
             self.forward_backward(constraints)
             return None
-        key = tuple((id(c), c._version, float(c.desc.scale)) for c in constraints) + ("deferred",)
+        key = tuple((id(c), c._version, c.scale_key) for c in constraints) + ("deferred",)
         self._step_graph.run(key, lambda: self._forward_backward_eager(constraints, reduce=False))
         return self._segments(constraints)
 
@@ -203,7 +409,7 @@ class SpinnEngine:
         # ONE launch (ppsci_reduce_rows_multi) sums every constraint's loss rows and the FIRST constraint's gradient rows -- segments
         # with different destinations; the other constraints' gradient rows are added behind it, one launch each, in order (they
         # share a destination).  Helmholtz3D's single PDE constraint: two launches (this one + Adam) instead of three.
-        segs = [(c.lpart, c.loss_term, c.lrows, 1) for c in constraints]
+        segs = [(c.lpart, c.loss_term, c.lrows, c.lcols) for c in constraints]
         c0 = constraints[0]
         if c0.gjoint:
             segs.append((c0.gpart_all, self.grad[:3 * P], c0.gpart_all.shape[0], 3 * P))
@@ -221,7 +427,7 @@ class SpinnEngine:
         # A step is ~12 launches per constraint of a few microseconds each (seven constraints in the reference's
         # Helmholtz3D example): launch-bound from Python, so the whole sequence is one replayed HIP graph.  The
         # residual scale and the grid shape are captured by value, hence part of the key.
-        key = tuple((id(c), c._version, float(c.desc.scale)) for c in constraints)
+        key = tuple((id(c), c._version, c.scale_key) for c in constraints)
         self._step_graph.run(key, lambda: self._forward_backward_eager(constraints))
 
     def invalidate_graphs(self) -> None:
