@@ -379,6 +379,34 @@ int ppsci_adam_step(int64_t n, float* params, const float* grad, float* m, float
                     float beta1, float beta2, float eps, int64_t step_t, float grad_scale,
                     void* stream);
 
+/* Per-loss gradient matrix kernels of the PCGrad / Relobralo loss aggregators.  G is [K, ld] fp32 (row k: the flat gradient
+ * of loss k, n <= ld columns used), K <= PPSCI_MTL_MAX_LOSSES.  No float atomics anywhere: two calls on the same input give
+ * the same bits.
+ *
+ * ppsci_grad_surgery replaces PCGrad._refine_grads (ppsci/loss/mtl/pcgrad.py:94-120): ONE launch.  Every workgroup writes its
+ * K(K+1)/2 partial dot products to the workspace, the workgroup that finishes last (an unsigned ticket in the workspace,
+ * left at zero for the next call) sums them in workgroup order and writes the symmetric gram_out[K*K].  With
+ * mode = PPSCI_MTL_GRAM_ONLY it stops there (order, coef_out, w_out are not read).  With mode = PPSCI_MTL_PCGRAD one thread
+ * then runs the projection rule in Gram space: g_i = sum_m C[i][m] g_m, C = I; for every i, for k = order[0 .. K-1] (HOST
+ * array, a permutation of 0 .. K-1, copied into the argument block):  C[i][k] -= min(sum_m C[i][m] Gram[m][k] / Gram[k][k], 0);
+ * it writes coef_out[K*K] = C and w_out[K], w_m = sum_i C[i][m], so that the reference's summed projected gradient is
+ * sum_m w_m g_m.  A row with Gram[k][k] == 0 is skipped as a projection target (the reference divides by it and returns NaN).
+ * workspace: ppsci_grad_surgery_workspace_bytes(K, n) bytes of device memory, ZEROED once by the caller. */
+#define PPSCI_MTL_MAX_LOSSES 8
+#define PPSCI_MTL_PCGRAD 0
+#define PPSCI_MTL_GRAM_ONLY 1
+int64_t ppsci_grad_surgery_workspace_bytes(int K, int64_t n);
+int ppsci_grad_surgery(int K, int64_t n, const float* G, int64_t ld, const int32_t* order, int mode, float* gram_out,
+                       float* coef_out, float* w_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* out[j] = sum_k w_k G[k][j], j < n, summed in the order k = 0 .. K-1 (PCGrad._set_grads, pcgrad.py:104-124; the
+ * lambda-weighted total of Relobralo, relobralo.py:121).  Exactly one of w_dev (DEVICE array of K floats, e.g. w_out above:
+ * no host round trip) and w_host (HOST array, copied into the argument block) is given.  With adam != NULL the update of
+ * ppsci_adam_step (same formula, grad_scale and step_t; params, adam->m, adam->v hold n floats) is applied from out[j] in the
+ * same launch; out still receives the combined gradient.  Any n and ld >= n: float4 accesses are used only where every row
+ * start is 16-byte aligned. */
+int ppsci_grad_combine(int K, int64_t n, const float* G, int64_t ld, const float* w_dev, const float* w_host, float* out,
+                       float* params, const ppsci_adam_args* adam, void* stream);
+
 /* The other first-order optimizers of ppsci/optimizer/optimizer.py (SGD :39-83, Momentum :86-176, RMSProp :326-383,
  * AdamW :386-495) as one fused update of the flat parameter buffer.  hyper (HOST array of 7 floats):
  *   [0] lr  [1] grad_scale  [2] L2Decay coefficient (added to the gradient)  [3..6] a, b, c, d

@@ -26,6 +26,8 @@ EMBED_NONE, EMBED_PERIOD, EMBED_STREAMS = 0, 1, 2
  OP_DETACH, OP_ASIN, OP_ACOS, OP_ATAN, OP_ATAN2, OP_ASINH, OP_ACOSH, OP_ATANH, OP_ERF, OP_LGAMMA, OP_CEIL, OP_FLOOR,
  OP_LD_PARAM, OP_COUNT) = range(38)
 MAX_EPARAM = 8
+MTL_MAX_LOSSES = 8  # PPSCI_MTL_MAX_LOSSES
+MTL_PCGRAD, MTL_GRAM_ONLY = 0, 1
 STEP_KEEP_FRAGMENTS = 1  # ppsci_taylor_step_run_ex flag (include/ppsci_hip.h)
 
 
@@ -335,6 +337,11 @@ _SYMBOLS = {
     "ppsci_spinn_jet_bwd": (C.c_int, [C.POINTER(SpinnJetDesc)] + [C.c_void_p] * 9),
     "ppsci_adam_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_int64, C.c_float, C.c_void_p]),
+    "ppsci_grad_surgery_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "ppsci_grad_surgery": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ppsci_grad_combine": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.c_void_p,
+                                     C.c_void_p, C.POINTER(AdamArgs), C.c_void_p]),
     "ppsci_optim_step": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "ppsci_causal_weights": (C.c_int, [C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

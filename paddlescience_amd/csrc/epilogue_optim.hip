@@ -663,3 +663,6 @@ extern "C" int ppsci_optim_step(int kind, int64_t n, float* params, const float*
   }
   return PPSCI_OK;
 }
+
+// ---- per-loss gradient matrix: Gram matrix + PCGrad rule, weighted combination (+ Adam)
+#include "grad_surgery.inc"

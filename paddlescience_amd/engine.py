@@ -533,14 +533,16 @@ class Engine:
         """Call after changing anything a captured launch holds by value (residual scales of an epilogue)."""
         self._step_graph.clear()
 
-    def allreduce(self) -> None:
+    def allreduce(self, buf: Optional[torch.Tensor] = None) -> None:
         # ONE collective per step: the flat fp32 gradient, SUM, in place, through torch.distributed (backend "nccl" is RCCL
         # over xGMI on ROCm; "gloo" in the CPU tests).  Matches fused_allreduce_gradients (/root/reference/ppsci/solver/train.py:168-171).
+        # `buf`: another contiguous fp32 buffer in its place (the [K, P] per-loss gradient matrix of PCGrad / Relobralo).
+        buf = self.grad if buf is None else buf
         if self.world > 1:
             if native_comm_ready():  # PPSCI_NATIVE_ALLREDUCE=1: the C ABI's RCCL communicator (csrc/comm.hip)
-                L.check(L.lib().ppsci_allreduce_sum(hp._p(self.grad), self.grad.numel(), hp._stream_ptr(self.grad)))
+                L.check(L.lib().ppsci_allreduce_sum(hp._p(buf), buf.numel(), hp._stream_ptr(buf)))
             else:
-                torch.distributed.all_reduce(self.grad, op=torch.distributed.ReduceOp.SUM)
+                torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM)
 
     def optimizer_step(self, lr: float) -> None:
         self.t += 1

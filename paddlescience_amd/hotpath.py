@@ -34,6 +34,12 @@ def _chk_f32(*ts):
             raise ValueError("hot-path buffers must be contiguous float32 tensors")
 
 
+def _adam_args(adam: dict) -> L.AdamArgs:
+    """ppsci_adam_args from the dict the engines pass around (m, v, lr, beta1, beta2, eps, grad_scale, t)."""
+    return L.AdamArgs(adam["m"].data_ptr(), adam["v"].data_ptr(), adam["lr"], adam["beta1"], adam["beta2"], adam["eps"],
+                      adam.get("grad_scale", 1.0), adam["t"])
+
+
 def _require_device(t: torch.Tensor):
     """The product path runs on the GPU only; CPU tensors are accepted solely under the emulator."""
     if not t.is_cuda and not L.is_emulated():
@@ -218,8 +224,7 @@ class StepPlan:
             self.scales = sc
         aa = None
         if adam is not None:
-            aa = C.byref(L.AdamArgs(adam["m"].data_ptr(), adam["v"].data_ptr(), adam["lr"], adam["beta1"], adam["beta2"],
-                                    adam["eps"], adam.get("grad_scale", 1.0), adam["t"]))
+            aa = C.byref(_adam_args(adam))
         # The tail kernel of a fused-tile step leaves the bf16 fragments of the updated hidden matrices behind; the next run
         # skips the weight-split launch when NOTHING has written the parameters in between: no kernel of this module
         # (param_writes counts adam_step / optim_step / the re-parametrisation kernels / other plans' fused Adam) and no torch
@@ -238,8 +243,7 @@ class StepPlan:
     def apply_adam(self, adam: dict) -> None:
         """Data parallelism: Adam from the finished (all-reduced) gradient of the plan + the fragments of the updated hidden
         matrices, one launch (ppsci_taylor_step_plan_apply)."""
-        aa = L.AdamArgs(adam["m"].data_ptr(), adam["v"].data_ptr(), adam["lr"], adam["beta1"], adam["beta2"], adam["eps"],
-                        adam.get("grad_scale", 1.0), adam["t"])
+        aa = _adam_args(adam)
         L.check(L.lib().ppsci_taylor_step_plan_apply(self.handle, C.byref(aa), _stream_ptr(self._dev)))
         note_param_write()
         capturing = self._params.is_cuda and torch.cuda.is_current_stream_capturing()
@@ -339,6 +343,65 @@ def adam_step(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torc
     note_param_write()
     L.check(L.lib().ppsci_adam_step(params.numel(), _p(params), _p(grad), _p(m), _p(v), lr, beta1, beta2, eps,
                                     step_t, grad_scale, _stream_ptr(params)))
+
+
+def _grad_matrix(G: torch.Tensor, n: Optional[int]) -> Tuple[int, int, int]:
+    """(K, n, ld) of a per-loss gradient matrix: a [K, ld] float32 tensor whose rows are contiguous (a column window of a
+    wider matrix is fine), the first n columns in use."""
+    if G.dim() != 2 or G.dtype != torch.float32 or G.stride(1) != 1:
+        raise ValueError("the per-loss gradient matrix is a [K, ld] float32 tensor with contiguous rows")
+    K, ld = G.shape[0], (G.stride(0) if G.shape[0] > 1 else G.shape[1])
+    n = G.shape[1] if n is None else int(n)
+    if n > G.shape[1]:
+        raise ValueError(f"n = {n} columns of a gradient matrix that has {G.shape[1]}")
+    return K, n, ld
+
+
+def grad_surgery_workspace_bytes(K: int, n: int) -> int:
+    return int(L.lib().ppsci_grad_surgery_workspace_bytes(K, n))
+
+
+def grad_surgery(G: torch.Tensor, gram: torch.Tensor, workspace: torch.Tensor, order: Optional[Sequence[int]] = None,
+                 coef: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None, mode: int = L.MTL_PCGRAD,
+                 n: Optional[int] = None) -> None:
+    """ppsci_grad_surgery: Gram matrix of the rows of G into `gram` [K*K] and, with mode = MTL_PCGRAD, the PCGrad rule in
+    Gram space for the projection order `order` (a host sequence: it travels in the argument block): `coef` [K*K] and the
+    combination weights `w` [K] stay on the device for grad_combine.  `workspace`: grad_surgery_workspace_bytes(K, n) bytes,
+    zeroed once (the kernel leaves its ticket at zero)."""
+    _require_device(G)
+    _chk_f32(gram, coef, w)
+    K, n, ld = _grad_matrix(G, n)
+    if gram.numel() < K * K or (coef is not None and coef.numel() < K * K) or (w is not None and w.numel() < K):
+        raise ValueError(f"grad_surgery: gram / coef hold K*K = {K * K} floats, w holds K = {K}")
+    od = None if order is None else (C.c_int32 * max(1, len(order)))(*[int(o) for o in order])
+    if order is not None and len(order) != K:
+        raise ValueError(f"order has {len(order)} entries for {K} losses")
+    L.check(L.lib().ppsci_grad_surgery(K, n, _p(G), ld, od, mode, _p(gram), _p(coef), _p(w), _p(workspace),
+                                       workspace.numel() * workspace.element_size(), _stream_ptr(G)))
+
+
+def grad_combine(G: torch.Tensor, out: torch.Tensor, w_dev: Optional[torch.Tensor] = None,
+                 w_host: Optional[Sequence[float]] = None, params: Optional[torch.Tensor] = None,
+                 adam: Optional[dict] = None, n: Optional[int] = None) -> None:
+    """ppsci_grad_combine: out[j] = sum_k w_k G[k, j] with the weights from the device (`w_dev`, e.g. grad_surgery's `w`) or
+    from the host (`w_host`); with `adam` (the dict of StepPlan.run) the Adam update of `params` from it in the same launch."""
+    _require_device(G)
+    _chk_f32(out, w_dev, params)
+    K, n, ld = _grad_matrix(G, n)
+    wh = None if w_host is None else (C.c_float * max(1, len(w_host)))(*[float(v) for v in w_host])
+    if w_host is not None and len(w_host) != K:
+        raise ValueError(f"w_host has {len(w_host)} entries for {K} losses")
+    if w_dev is not None and w_dev.numel() < K:
+        raise ValueError(f"w_dev has {w_dev.numel()} entries for {K} losses")
+    if out.numel() < n or (adam is not None and (params is None or min(params.numel(), adam["m"].numel(), adam["v"].numel()) < n)):
+        raise ValueError("grad_combine: out / params / m / v hold fewer than n floats")
+    aa = None
+    if adam is not None:
+        _chk_f32(adam["m"], adam["v"])
+        aa = C.byref(_adam_args(adam))
+    L.check(L.lib().ppsci_grad_combine(K, n, _p(G), ld, _p(w_dev), wh, _p(out), _p(params), aa, _stream_ptr(G)))
+    if adam is not None:
+        note_param_write()
 
 
 OPT_SGD, OPT_MOMENTUM, OPT_RMSPROP, OPT_ADAMW = 0, 1, 2, 3

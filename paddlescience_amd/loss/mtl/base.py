@@ -3,6 +3,8 @@
 
 class LossAggregator:
     should_persist = False
+    per_loss_grad = False  # GradNorm / NTK: the Solver supplies per-key gradient norms at update steps
+    grad_matrix = False    # PCGrad / Relobralo: the Solver combines the rows of a per-key gradient matrix every step
 
     def __init__(self, model=None) -> None:
         self.model = model

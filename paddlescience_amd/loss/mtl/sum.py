@@ -1,5 +1,5 @@
 """ppsci.loss.mtl.Sum (/root/reference/ppsci/loss/mtl/sum.py:27-60): left fold `+=` over the loss dict in
-insertion order.  (GradNorm / NTK: grad_weight.py; AGDA / PCGrad / Relobralo are not implemented.)"""
+insertion order.  (GradNorm / NTK: grad_weight.py; PCGrad / Relobralo: surgery.py, where AGDA raises with the reason.)"""
 from .base import LossAggregator
 
 

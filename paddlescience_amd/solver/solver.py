@@ -7,7 +7,7 @@ program) and a training iteration is a fixed sequence of kernel launches (engine
 are only read back (one device->host sync) every `log_freq` iterations, whereas the reference syncs on
 `.item()` for every loss term of every iteration (expression.py:122, train.py:145).
 Visualizers (`visualizer=`, `visualize()`) evaluate their expressions through `predict` and hand the arrays to
-`ppsci.visualize`'s writers.  Not supported (raise): AMP, to_static, loss aggregators other than Sum / GradNorm / NTK."""
+`ppsci.visualize`'s writers.  Not supported (raise): AMP, to_static, the AGDA loss aggregator."""
 from __future__ import annotations
 
 import datetime
@@ -26,6 +26,7 @@ from ..device import get_device
 from ..engine import Engine
 from ..loss import mtl
 from ..utils import logger, misc, save_load
+from .._lib import MTL_MAX_LOSSES
 
 
 def _metric_value(v):
@@ -84,8 +85,9 @@ class Solver:
         if int(update_freq) < 1:
             raise ValueError(f"update_freq should be a positive integer, but got {update_freq}")
         if loss_aggregator is not None and not (isinstance(loss_aggregator, mtl.Sum)
-                                                or getattr(loss_aggregator, "per_loss_grad", False)):
-            raise NotImplementedError("loss aggregators on the fused path: Sum, GradNorm, NTK")
+                                                or getattr(loss_aggregator, "per_loss_grad", False)
+                                                or getattr(loss_aggregator, "grad_matrix", False)):
+            raise NotImplementedError("loss aggregators on the fused path: Sum, GradNorm, NTK, PCGrad, Relobralo")
         self.cfg = cfg
         if cfg is not None and hasattr(cfg, "get") and cfg.get("TRAIN", None) is not None or (
                 cfg is not None and hasattr(cfg, "get") and cfg.get("output_dir", None) is not None):
@@ -176,6 +178,14 @@ class Solver:
         # factored / tied layers (weight_norm, random_weight, fourier): the kernels read model.kernel_params,
         # rebuilt from the trainable tensors before every sweep; their gradient is pulled back afterwards
         self._reparam = bool(getattr(self.model, "reparam", False))
+        # per-key gradients by masked passes: GradNorm / NTK at their update steps, PCGrad / Relobralo in every step -- nothing
+        # may fuse the optimizer into the pass that produces the gradient
+        self._key_grads = bool(getattr(self.loss_aggregator, "per_loss_grad", False)
+                               or getattr(self.loss_aggregator, "grad_matrix", False))
+        self._mtl = None  # PCGrad / Relobralo: the [K, P] gradient matrix and the small device buffers around it
+        self._mtl_total = 0.0  # Relobralo: the re-weighted total of the last step (what gets logged)
+        if getattr(self.loss_aggregator, "grad_matrix", False):
+            self._check_grad_matrix_supported()
         self._acc_grad, self._acc_count = None, 0  # gradient accumulation (update_freq > 1)
         self.latest_save_interval = float(os.environ.get("PPSCI_LATEST_SAVE_INTERVAL", "1.0"))  # seconds; 0 = every epoch
         self._latest_saved_at = float("-inf")
@@ -394,6 +404,8 @@ class Solver:
                         return total, g * gscale if gscale != 1.0 else g
 
                     self.optimizer.step(closure)
+                elif getattr(self.loss_aggregator, "grad_matrix", False):
+                    self._step_grad_matrix(eng_csts, gscale)  # PCGrad / Relobralo: K masked passes, surgery, combine (+ Adam)
                 elif self._step_in_one_launch(eng_csts, gscale):
                     pass  # forward -> loss -> backward -> Adam of every constraint in one launch each (engine.step_one_launch)
                 elif self._reduce_and_adam_in_one_launch(eng_csts, gscale):
@@ -480,14 +492,14 @@ class Solver:
 
     def _apply_loss_weights(self, mask_key=None):
         """Residual scale = base scale x weight of its key (or, for a masked pass, base scale for one key and 0)."""
-        agg = self.loss_aggregator
         keys = self._loss_key_order()
+        weight = getattr(self.loss_aggregator, "weight", None)  # (PCGrad / Relobralo weight gradients, not residual scales)
         for cc in self._compiled.values():
             if not hasattr(cc, "_base_scales"):
                 cc._base_scales = [cc.fused.edesc.res[i].scale for i in range(len(cc.label_keys))]
             for i, k in enumerate(cc.label_keys):
                 if mask_key is None:
-                    cc.fused.edesc.res[i].scale = cc._base_scales[i] * float(agg.weight[keys.index(k)])
+                    cc.fused.edesc.res[i].scale = cc._base_scales[i] * (1.0 if weight is None else float(weight[keys.index(k)]))
                 else:
                     cc.fused.edesc.res[i].scale = cc._base_scales[i] if k == mask_key else 0.0
         self.engine.invalidate_graphs()
@@ -548,7 +560,7 @@ class Solver:
         constraint small enough for the one-launch kernel (engine.one_launch_ready).  False: nothing was done."""
         opt = self.optimizer
         if (self.world_size != 1 or not eng_csts or self._reparam or self.update_freq > 1
-                or getattr(self.loss_aggregator, "per_loss_grad", False) or type(opt).__name__ != "_AdamState"
+                or self._key_grads or type(opt).__name__ != "_AdamState"
                 or opt.grad_clip is not None or opt.l2 != 0.0 or opt.eq_store is not None
                 or not hasattr(self.engine, "one_launch_ready") or opt.model.flat_params.data_ptr() != self.engine.params.data_ptr()
                 or not self.engine.one_launch_ready(eng_csts)):
@@ -581,7 +593,7 @@ class Solver:
         opt, eng = self.optimizer, self.engine
         if (self.world_size != 1 or not hasattr(eng, "forward_backward_deferred") or type(opt).__name__ != "_AdamState"
                 or opt.grad_clip is not None or opt.l2 != 0.0 or opt.eq_store is not None or self.update_freq > 1 or self._reparam
-                or getattr(self.loss_aggregator, "per_loss_grad", False) or os.environ.get("PPSCI_FUSED_REDUCE_ADAM", "1") == "0"
+                or self._key_grads or os.environ.get("PPSCI_FUSED_REDUCE_ADAM", "1") == "0"
                 or opt.model.flat_params.data_ptr() != self.model.flat_params.data_ptr()):
             return False
         from ..engine import step_with_adam
@@ -613,6 +625,121 @@ class Solver:
         for cc, t in zip(self._compiled.values(), saved_terms):
             cc.fused.loss_terms.copy_(t)
 
+    # ------------------------------------------------------------------ per-loss gradient matrix (PCGrad / Relobralo)
+    def _check_grad_matrix_supported(self) -> None:
+        name = type(self.loss_aggregator).__name__
+        if self._is_spinn or self._is_operator:
+            raise NotImplementedError(f"{name} needs the fused PINN engine (one masked pass per loss key), as GradNorm / NTK do; "
+                                      "SPINN and operator models have no masked pass")
+        if getattr(self.optimizer, "is_lbfgs", False):
+            raise NotImplementedError(f"{name} with L-BFGS: the line search re-evaluates ONE scalar loss and its gradient, the "
+                                      "combined gradient of per-loss surgery is the gradient of no such loss")
+        if self.update_freq > 1:
+            raise NotImplementedError(f"{name} with update_freq > 1: the reference's _set_grads overwrites param.grad "
+                                      "(ppsci/loss/mtl/pcgrad.py:122-124), so what accumulation means there is undefined")
+        if self._extra_parameters() or getattr(self.optimizer, "eq_store", None) is not None:
+            raise NotImplementedError(f"{name} with learnable equation parameters: the per-loss gradient matrix holds the "
+                                      "network's parameters only")
+
+    def _grad_matrix_buffers(self, K: int, P: int):
+        """One flat buffer: the [K, ld] gradient matrix (ld = P rounded up to 4 floats, so that every row starts 16-byte aligned
+        and the kernels take their float4 paths) and, behind it, 3K + 1 slots that travel in the same all-reduce under data
+        parallelism: the K loss values of this rank, rank 0's projection order (K) and rho (1), the constant parts of the K
+        terms (FusedConstraint.loss_offsets)."""
+        if self._mtl is None or self._mtl["G"].shape != (K, P):
+            if K > MTL_MAX_LOSSES:
+                raise NotImplementedError(f"{type(self.loss_aggregator).__name__}: {K} loss keys; the surgery kernels hold "
+                                          f"{MTL_MAX_LOSSES} (PPSCI_MTL_MAX_LOSSES)")
+            dev = self.engine.grad.device
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            ld = (P + 3) & ~3
+            buf = z(K * ld + ((3 * K + 1 + 3) & ~3))
+            keys = self._loss_key_order()
+            self._mtl = dict(buf=buf, G=buf[:K * ld].view(K, ld)[:, :P], slots=buf[K * ld:], gram=z(K * K), coef=z(K * K), w=z(K),
+                             out=z(P) if self._reparam else self.engine.grad,
+                             ws=z((hp.grad_surgery_workspace_bytes(K, P) + 3) // 4),
+                             terms=[torch.zeros_like(cc.fused.loss_terms) for cc in self._compiled.values()],
+                             term_keys=[torch.tensor([keys.index(k) for k in cc.label_keys], dtype=torch.long, device=dev)
+                                        for cc in self._compiled.values()])
+        return self._mtl
+
+    def _share_over_ranks(self, b, keys, order, rho, gscale: float):
+        """Data parallelism: ONE all-reduce of the gradient matrix and its slots.  Every rank has drawn `order` / `rho` from its
+        own numpy generator (so the ranks consume their streams alike), but the surgery runs behind the all-reduce on every rank:
+        what they apply must be ONE draw, or their parameter copies drift apart unnoticed.  Rank 0's travels in the slots (the
+        others contribute zeros), next to every rank's share of the K loss values.  Returns (global losses, order, rho); reading
+        the slots back is the step's device-to-host transfer under data parallelism."""
+        K, slots = len(keys), b["slots"]
+        slots.zero_()
+        for cc, acc, idx in zip(self._compiled.values(), b["terms"], b["term_keys"]):
+            slots[:K].index_add_(0, idx, acc[:idx.numel()])
+        host = [0.0] * (2 * K + 1)
+        if self.rank == 0:
+            host[:K] = [float(o) for o in (order if order is not None else [0] * K)]
+            host[K] = float(rho)
+        for cc in self._compiled.values():
+            for k, v in (getattr(cc.fused, "loss_offsets", None) or {}).items():
+                host[K + 1 + keys.index(k)] += float(v)
+        slots[K:3 * K + 1].copy_(torch.tensor(host, dtype=torch.float32))
+        self.engine.allreduce(b["buf"])
+        vals = slots[:3 * K + 1].tolist()
+        # (dp_reduce = "mean": the loss whose gradient is applied is 1 / world of the sum, as in the L-BFGS closure)
+        losses = {k: (vals[i] + vals[2 * K + 1 + i]) * gscale for i, k in enumerate(keys)}
+        return losses, [int(round(v)) for v in vals[K:2 * K]], vals[2 * K]
+
+    def _step_grad_matrix(self, eng_csts, gscale: float) -> None:
+        """One training step under PCGrad / Relobralo (pcgrad.py:62-124, relobralo.py:90-127): the flat gradient of every loss key
+        by a masked pass into row k of a persistent [K, P] matrix (with re-parametrised layers the pulled-back gradient: the
+        reference's param.grad), ONE all-reduce of the whole matrix under data parallelism (_share_over_ranks), then
+          PCGrad:    hp.grad_surgery (Gram matrix + projection rule, weights stay on the device) -> hp.grad_combine;
+          Relobralo: the K raw loss values to the host (this step's one sync), the host rule -> hp.grad_combine.
+        grad_combine applies Adam in the same launch when the optimizer is a plain Adam (no clipping, no decay); otherwise it
+        leaves the combined gradient for optimizer.step.  On one rank PCGrad's step has no device-to-host transfer."""
+        agg, opt = self.loss_aggregator, self.optimizer
+        keys = self._loss_key_order()
+        self._materialize()
+        g0 = None
+        for k, key in enumerate(keys):
+            self._apply_loss_weights(mask_key=key)
+            self.engine.forward_backward(eng_csts)
+            g = self._train_grad()
+            if g0 is None:
+                g0, b = g, self._grad_matrix_buffers(len(keys), g.numel())
+            hp.reduce_rows(g.view(1, -1), 1, g.numel(), b["G"][k], False)
+            # the masked pass leaves key's raw terms and zeros for the others: summed over the passes, every raw term
+            for cc, acc in zip(self._compiled.values(), b["terms"]):
+                hp.reduce_rows(cc.fused.loss_terms.view(1, -1), 1, acc.numel(), acc.view(-1), k > 0)
+        self._apply_loss_weights()
+        for cc, acc in zip(self._compiled.values(), b["terms"]):
+            cc.fused.loss_terms.copy_(acc)
+        # the step's random draws, on every rank (pcgrad.py:64-65; relobralo.py:107, which draws from step 1 on)
+        order = agg.draw_order(keys) if agg.device_rule else None
+        rho = agg.draw_rho() if (not agg.device_rule and self.global_step != 0) else 0.0
+        losses = None
+        if self.world_size > 1:
+            losses, order, rho = self._share_over_ranks(b, keys, order, rho, gscale)
+        adam = None
+        if (type(opt).__name__ == "_AdamState" and opt.grad_clip is None and opt.l2 == 0.0 and opt.eq_store is None
+                and opt.model.flat_params.numel() == g0.numel()):
+            adam = dict(m=opt.m, v=opt.v, lr=opt.get_lr(), beta1=opt.beta1, beta2=opt.beta2, eps=opt.epsilon,
+                        grad_scale=gscale, t=opt.t + 1)
+        params = opt.model.flat_params if adam is not None else None
+        if agg.device_rule:
+            hp.grad_surgery(b["G"], b["gram"], b["ws"], order, b["coef"], b["w"])
+            hp.grad_combine(b["G"], b["out"], w_dev=b["w"], params=params, adam=adam)
+        else:
+            if losses is None:
+                losses = dict.fromkeys(keys, 0.0)
+                for cc in self._compiled.values():
+                    for k, v in cc.fused.losses().items():
+                        losses[k] += v
+            self._mtl_total = agg(losses, self.global_step, rho=rho)
+            hp.grad_combine(b["G"], b["out"], w_host=agg.weights(), params=params, adam=adam)
+        if adam is not None:
+            opt.t += 1
+        else:
+            opt.step(b["out"], gscale)
+
     def _update_train_loss(self):
         """printer.update_train_loss: total `loss` = Sum aggregator over all terms (mtl/sum.py:45-60), plus one
         entry per constraint = sum of its keys (expression.py:120-126)."""
@@ -633,7 +760,10 @@ class Solver:
             for k in keys:
                 per_cst[name] += vals[k]
                 losses_all[k] = losses_all.get(k, 0.0) + vals[k]
-        total = float(self.loss_aggregator(losses_all, self.global_step))
+        if getattr(self.loss_aggregator, "grad_matrix", False) and not self.loss_aggregator.device_rule:
+            total = float(self._mtl_total)  # Relobralo: sum_k lambda_k L_k of the step (its __call__ advances the state)
+        else:
+            total = float(self.loss_aggregator(losses_all, self.global_step))
         if self.update_freq > 1:
             total /= self.update_freq  # train.py:141-142: the logged total is the scaled one
         self.last_losses = {"loss": total, **per_cst}
