@@ -6,6 +6,7 @@ This is the counterpart of `Solver.__init__`'s `convert_expr` (/root/reference/p
 what the reference re-executes op by op every iteration is decided here once."""
 from __future__ import annotations
 
+import os
 import zlib
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -331,6 +332,12 @@ class CompiledConstraint:
         self._row_slice_cache = (key, {k: (label[k], weight[k]) for k in self._row_slices}, sources)
         return label, weight
 
+    step_obj = property(lambda self: self.fused)
+
+    def losses(self) -> Dict[str, float]:
+        vals = self.fused.losses()
+        return {k: vals[k] for k in self.label_keys}
+
     def values(self) -> Dict[str, torch.Tensor]:
         """Per-point values of every loss key / extra output ([n,1] tensors), after a forward."""
         assert self.fused.resid is not None
@@ -339,3 +346,38 @@ class CompiledConstraint:
             if k in out:
                 out[k] = out[k][a:a + 1]
         return out
+
+
+def check_trace_decisions(name: str, cc: Optional[CompiledConstraint], world: int, failure: Optional[str] = None) -> None:
+    """Python control flow on the values of a fixed batch is followed at trace time (graph.batch_values).  Under data
+    parallelism every rank traces on ITS shard: the ranks must end up with the SAME program (residual program, loss terms,
+    derivative streams), otherwise they would train different programs against one all-reduced gradient without anybody
+    noticing (the reference evaluates the user's function on each rank's tensors every step, utils/expression.py:96-102, so
+    there a rank-dependent branch is at least visible in the loss).  A collective: every rank calls it for every
+    constraint, in the same order."""
+    dist = torch.distributed
+    if world <= 1 or not dist.is_available() or not dist.is_initialized():
+        return
+    if cc is None:  # this rank's trace raised: say so to everybody instead of leaving them in the collective
+        mine = (None, None, [], failure or "trace failed")
+    else:
+        mine = (zlib.crc32(bytes(cc.fused.edesc)), repr(cc.fused.streams), list(cc.specialised_to), None)
+    everyone = [None] * dist.get_world_size()
+    dist.all_gather_object(everyone, mine)
+    failed = [(r, e[3]) for r, e in enumerate(everyone) if e[3] is not None]
+    if failed:
+        if cc is None:
+            return  # the caller raises this rank's own reason
+        raise NotImplementedError(f"constraint {name}: not lowerable on rank {failed[0][0]} ({failed[0][1]}); its shard takes "
+                                  "a path through the expressions that this rank's shard does not")
+    if any(e[:2] != everyone[0][:2] for e in everyone):
+        from .utils import logger
+
+        odd = next(r for r, e in enumerate(everyone) if e[:2] != everyone[0][:2])
+        msg = (f"constraint {name}: the expressions branch on values of the batch and ranks 0 and {odd} took different "
+               f"branches (rank 0 asked {everyone[0][2]}; rank {odd} asked {everyone[odd][2]}): their programs differ")
+        if os.environ.get("PPSCI_RANK_SPECIFIC_TRACES", "0") == "1":
+            logger.warning(msg + " -- accepted (PPSCI_RANK_SPECIFIC_TRACES=1): every rank trains its own program")
+        else:
+            raise RuntimeError(msg + "; make the condition independent of the shard, or set PPSCI_RANK_SPECIFIC_TRACES=1 "
+                                     "to train rank-specific programs")

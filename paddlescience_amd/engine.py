@@ -8,6 +8,22 @@ One step == `train_epoch_func` body of the reference (/root/reference/ppsci/solv
   optimizer.step(); clear_grad()                                    (train.py:175-180)
 Here: taylor_fwd -> epilogue -> taylor_bwd per constraint, one reduce_rows into the flat gradient,
 one RCCL all-reduce (torch.distributed, SUM) of that flat buffer when world_size > 1, one fused Adam.
+
+The engine contract.  solver.Solver picks ONE engine per model family -- `Engine` here (point nets), spinn_engine.SpinnEngine,
+operator_engine.OperatorEngine -- and then asks the engine and its compiled constraints (compile.CompiledConstraint,
+SpinnConstraint / SpinnJetConstraint, OperatorConstraint), never the family:
+  engine.grad, .dp_reduce, .world     the flat gradient of a step, "sum" | "mean" over the ranks, the rank count
+  engine.forward_backward(steps)      gradient and loss terms of one step; `steps` = [cc.step_obj for every constraint]
+  engine.allreduce(buf=None)          SUM over the ranks of `grad`, or of `buf` in its place -- every engine honours `buf`
+  engine.invalidate_graphs()          forget captured steps (something they hold by value has changed)
+  engine.per_key_pass                 flag: a masked pass per loss key exists (GradNorm / NTK / PCGrad / Relobralo need it)
+  cc.step_obj, cc.bind(input, label, weight), cc.label_keys, cc.batch_size
+  cc.losses() -> {key: float}         the loss terms of the last step, for logging (the step's device-to-host sync)
+Optional, probed with hasattr: the fused optimizer steps of Solver.train (one_launch_ready / step_one_launch / apply_adam_fused
+here, forward_backward_deferred / flush_deferred on the other two), and compile_constraint(name, cst, device, world, rank),
+eval_validator(val, device), predict(input_dict, expr_dict, batch_size, return_numpy, device) for an engine that does that job
+itself.  `Engine` has none of these three: the Solver compiles the constraints, validators and predictions of point nets, next
+to the data-parallel state that CompiledConstraint depends on (batch-size rules, ragged shards, compile.check_trace_decisions).
 """
 from __future__ import annotations
 
@@ -424,6 +440,8 @@ def _release_fragments(ptr: int) -> None:
 
 
 class Engine:
+    per_key_pass = True  # a masked pass per loss key: zero the other keys' residual scales (Solver._apply_loss_weights)
+
     def __init__(self, layout: hp.NetLayout, params: torch.Tensor, beta1=0.9, beta2=0.999, eps=1e-8,
                  dp_reduce: str = "sum"):
         assert layout is None or params.numel() == layout.n_params  # None: several networks (ModelList)
@@ -563,16 +581,17 @@ class Engine:
             return True
         return False
 
+    def _adam_args(self, lr: float, grad_scale: float, t: int) -> dict:
+        return dict(m=self.m, v=self.v, lr=lr, beta1=self.beta1, beta2=self.beta2, eps=self.eps, grad_scale=grad_scale, t=t)
+
     def train_step(self, constraints: Sequence[FusedConstraint], lr: float) -> None:
         if self.world == 1 and self.one_launch_ready(constraints):
             self.t += 1
-            return self.step_one_launch(constraints, dict(m=self.m, v=self.v, lr=lr, beta1=self.beta1, beta2=self.beta2,
-                                                          eps=self.eps, grad_scale=1.0, t=self.t))
+            return self.step_one_launch(constraints, self._adam_args(lr, 1.0, self.t))
         self.forward_backward(constraints)
         self.allreduce()
         scale = (1.0 / self.world) if (self.dp_reduce == "mean" and self.world > 1) else 1.0
-        if self.apply_adam_fused(constraints, dict(m=self.m, v=self.v, lr=lr, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
-                                                   grad_scale=scale, t=self.t + 1)):
+        if self.apply_adam_fused(constraints, self._adam_args(lr, scale, self.t + 1)):
             self.t += 1
             return
         self.optimizer_step(lr)

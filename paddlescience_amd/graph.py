@@ -170,7 +170,7 @@ class Sym:
             # a fixed batch, but the compared values depend on the network: no answer at trace time, a traced indicator
             return self._indicator(o, what)
         # (the ANSWER is part of the record: ranks of a data-parallel job see different shards and must not silently compile
-        # different programs, solver.Solver._check_trace_decisions)
+        # different programs, compile.check_trace_decisions)
         if v.size == 1:
             ans = bool(v.reshape(-1)[0])
             _TRACE.concretized.append(f"{what}({self!r}) = {ans!r}")

@@ -2,8 +2,8 @@
 kernels (the model's executor, native_executor.NativeExecutor), the loss and its adjoint w.r.t. the network output from the
 loss object's own kernels
 (loss.field: LpLoss / H1Loss / MSELoss on fields) -- gradients land in the model's flat buffer, one SUM all-reduce of that
-buffer per step and the fused Adam kernel on it: the same contract (`forward_backward`, `allreduce`, `grad`,
-`dp_reduce`) as `engine.Engine` for the PINN path.
+buffer per step and the fused Adam kernel on it.  OperatorEngine and OperatorConstraint implement the engine contract
+stated in engine.py's docstring.
 
 Mirrors ExpressionSolver.train_forward + train_epoch_func for a supervised constraint
 (/root/reference/ppsci/utils/expression.py:60-131, ppsci/solver/train.py:58-213)."""
@@ -58,6 +58,8 @@ class OperatorConstraint:
         else:
             self.inp, self.lab, self.w = new
             self.version += 1
+
+    step_obj = property(lambda self: self)
 
     def outputs(self) -> Dict[str, torch.Tensor]:
         out = self.model(self.inp)
@@ -114,6 +116,7 @@ class OperatorConstraint:
 
 class OperatorEngine:
     dp_reduce = "mean"  # DataParallel semantics of the reference: gradients are averaged over ranks
+    per_key_pass = False
 
     def __init__(self, model):
         self.model = model
@@ -160,6 +163,48 @@ class OperatorEngine:
     def flush_deferred(self, segs) -> None:
         self.native.flush_wgrads(segs)
 
-    def allreduce(self):
+    def invalidate_graphs(self) -> None:
+        self._step_graph.clear()
+
+    def allreduce(self, buf: Optional[torch.Tensor] = None):
         if self.world > 1:
-            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
+            dist.all_reduce(self.grad if buf is None else buf, op=dist.ReduceOp.SUM)
+
+    def compile_constraint(self, name: str, cst, device, world: int = 1, rank: int = 0) -> OperatorConstraint:
+        ds = getattr(cst.data_loader, "dataset", cst.data_loader)
+        bsz = getattr(getattr(cst.data_loader, "batch_sampler", None), "batch_size", 0) or 0
+        return OperatorConstraint(name, self.model, cst.output_expr, cst.loss, device, list(ds.label_keys), bsz)
+
+    def eval_validator(self, val, device):
+        """eval.py _eval_by_dataset through torch: the validator's values and labels ({key: [batches]}), the mean batch loss."""
+        outs: Dict[str, list] = {}
+        labs: Dict[str, list] = {}
+        loss_sum, nb = 0.0, 0
+        self.model.eval()
+        with torch.no_grad():
+            for (inp, lab, w) in val.data_loader:
+                inp_d, lab_d, w_d = _to_dev(inp, device), _to_dev(lab, device), _to_dev(w, device)
+                data = {**inp_d, **self.model(inp_d)}
+                vals = {k: f(data) for k, f in val.output_expr.items()}
+                loss_sum += float(sum(val.loss(vals, lab_d, w_d).values()))
+                nb += 1
+                for k in vals:
+                    outs.setdefault(k, []).append(vals[k])
+                for k in lab_d:
+                    labs.setdefault(k, []).append(lab_d[k])
+        self.model.train()
+        return outs, labs, loss_sum / max(nb, 1)
+
+    def predict(self, input_dict, expr_dict, batch_size, return_numpy: bool, device):
+        n = len(next(iter(input_dict.values())))
+        bs = n if batch_size is None else batch_size
+        exprs = expr_dict if expr_dict is not None else {k: (lambda out, k=k: out[k]) for k in self.model.output_keys}
+        res: Dict[str, list] = {k: [] for k in exprs}
+        with torch.no_grad():
+            for s0 in range(0, n, bs):
+                chunk = _to_dev({k: v[s0:s0 + bs] for k, v in input_dict.items()}, device)
+                data = {**chunk, **self.model(chunk)}
+                for k, f in exprs.items():
+                    res[k].append(f(data))
+        pred = {k: torch.cat(v, 0) for k, v in res.items()}
+        return {k: v.cpu().numpy() for k, v in pred.items()} if return_numpy else pred

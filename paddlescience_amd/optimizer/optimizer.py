@@ -173,6 +173,15 @@ class Adam:
         return st
 
 
+def fused_adam_args(opt, grad_scale: float, t: int) -> Optional[dict]:
+    """May the kernel that produces the gradient apply `opt`'s update in its own launch?  Only for a plain Adam (the state that
+    `Adam.__call__` makes, without clipping, L2 decay or learnable equation parameters): the `adam` argument of those kernels for
+    step number `t`, else None.  The ONE test of what "plain Adam" means; callers add the conditions of their own launch."""
+    if not isinstance(opt, _AdamState) or opt.grad_clip is not None or opt.l2 != 0.0 or opt.eq_store is not None:
+        return None
+    return dict(m=opt.m, v=opt.v, lr=opt.get_lr(), beta1=opt.beta1, beta2=opt.beta2, eps=opt.epsilon, grad_scale=grad_scale, t=t)
+
+
 def _single(model_list):
     if isinstance(model_list, (list, tuple)):
         if len(model_list) != 1:

@@ -10,21 +10,22 @@ Visualizers (`visualizer=`, `visualize()`) evaluate their expressions through `p
 `ppsci.visualize`'s writers.  Not supported (raise): AMP, to_static, the AGDA loss aggregator."""
 from __future__ import annotations
 
+import contextlib
 import datetime
 import os
 import time
-from typing import Any, Callable, Dict, Mapping, Optional, Sequence, Tuple, Union
+from typing import Any, Callable, Dict, Mapping, Optional, Tuple, Union
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from .. import autodiff
 from .. import hotpath as hp
-from ..compile import CompiledConstraint
+from ..compile import CompiledConstraint, check_trace_decisions
 from ..device import get_device
 from ..engine import Engine
 from ..loss import mtl
+from ..optimizer.optimizer import fused_adam_args
 from ..utils import logger, misc, save_load
 from .._lib import MTL_MAX_LOSSES
 
@@ -161,15 +162,14 @@ class Solver:
         if self.world_size > 1:
             # DataParallel wrap of the reference (solver.py:388-412): replicate rank 0's parameters
             dist.broadcast(self.model.flat_params, src=0)
+        # ONE engine per model family; from here on the engine and its compiled constraints are asked (the contract: engine.py)
         from ..arch.spinn import SPINN
 
-        self._is_spinn = isinstance(self.model, SPINN)
-        self._is_operator = bool(getattr(self.model, "is_operator", False))
-        if self._is_spinn:
+        if isinstance(self.model, SPINN):
             from ..spinn_engine import SpinnEngine
 
             self.engine = SpinnEngine(self.model)
-        elif self._is_operator:
+        elif getattr(self.model, "is_operator", False):
             from ..operator_engine import OperatorEngine
 
             self.engine = OperatorEngine(self.model)
@@ -189,18 +189,11 @@ class Solver:
         self._acc_grad, self._acc_count = None, 0  # gradient accumulation (update_freq > 1)
         self.latest_save_interval = float(os.environ.get("PPSCI_LATEST_SAVE_INTERVAL", "1.0"))  # seconds; 0 = every epoch
         self._latest_saved_at = float("-inf")
-        if (self.optimizer is not None and not self._is_spinn and not self._is_operator and not self._reparam
-                and hasattr(self.optimizer, "beta1")):
-            self.engine.m, self.engine.v = self.optimizer.m, self.optimizer.v
-            self.engine.beta1, self.engine.beta2, self.engine.eps = (self.optimizer.beta1, self.optimizer.beta2,
-                                                                    self.optimizer.epsilon)
-            self.engine.t = self.optimizer.t
 
         # ---- compile constraints (convert_expr, solver.py:496-535)
         self._compiled: Dict[str, CompiledConstraint] = {}
         self._static: Dict[str, bool] = {}
         self._ragged: set = set()  # constraints whose sample count does not divide over the ranks (zero-weight padding)
-        self._device_data: Dict[str, Tuple[dict, dict, dict]] = {}
         if self.constraint:
             for name, cst in self.constraint.items():
                 self._compiled[name] = self._compile_constraint(name, cst)
@@ -208,83 +201,10 @@ class Solver:
         self._predict_cache: Dict[tuple, CompiledConstraint] = {}
 
     # ------------------------------------------------------------------ compilation helpers
-    def _equation_exprs(self, exprs: Dict[str, Callable]) -> Dict[str, Callable]:
-        return dict(exprs)
-
-    def _compile_spinn_constraint(self, name: str, cst):
-        """Separable nets.  One residual that is a linear form of {u, u_xx, u_yy, u_zz} without weights keeps the
-        four-coefficient grid kernels (arch.spinn.GridLinear -> SpinnConstraint); everything else -- several keys, weight grids,
-        non-linear residuals, first and mixed derivatives -- is lowered to an epilogue program over the derivative streams it
-        reads (SpinnJetConstraint).  PPSCI_SPINN_JET=1 sends a linear form down the general path too (A/B timing, tests)."""
-        from ..arch.spinn import GridLinear
-        from ..graph import Sym
-        from ..spinn_engine import SpinnConstraint
-
-        ds = getattr(cst.data_loader, "dataset", cst.data_loader)
-        label_keys = list(ds.label_keys)
-        if hasattr(ds, "weight_fn"):  # ContinuousNamedArrayDataset
-            w0 = ds.weight_fn(ds.input_fn()) if callable(ds.weight_fn) else None
-            weight_keys = list(w0.keys()) if w0 else []
-        else:
-            weight_keys = list((getattr(ds, "weight", None) or {}).keys())
-        data = {k: Sym.input(k) for k in self.model.input_keys}
-        data.update(self.model(data))
-        vals = {k: (cst.output_expr[k](data) if k in cst.output_expr else data[k]) for k in label_keys}
-        autodiff.clear()
-        loss = cst.loss
-        key = label_keys[0] if label_keys else None
-        linear = (len(label_keys) == 1 and not weight_keys and isinstance(vals[key], GridLinear)
-                  and getattr(loss, "term_kind", 0) == 0 and os.environ.get("PPSCI_SPINN_JET", "0") != "1")
-        if linear:
-            sc = SpinnConstraint(name, self.model, vals[key].c, key, lambda total, k=key: loss.term_scale(k, total), self.device,
-                                 self.world_size, self.rank)
-        else:
-            sc = self._spinn_jet_constraint(name, vals, label_keys, weight_keys, loss)
-        sc.batch_size = 0
-        sc.label_keys = label_keys
-        return sc
-
-    def _spinn_jet_constraint(self, name, vals, label_keys, weight_keys, loss, extra_outputs=()):
-        """Lowers traced SPINN expressions with graph.lower (the program builder of every other model) on a stream table of
-        per-axis derivative orders."""
-        from .. import _lib, graph
-        from ..arch.spinn import JetTable
-        from ..compile import LABEL_PREFIX, WEIGHT_PREFIX
-        from ..spinn_engine import SpinnJetConstraint
-
-        if len(label_keys) + len(extra_outputs) > _lib.MAX_RES:
-            raise NotImplementedError(f"constraint {name}: {len(label_keys) + len(extra_outputs)} expression keys; one epilogue "
-                                      f"program holds {_lib.MAX_RES} (PPSCI_MAX_RES)")
-        if weight_keys and hasattr(loss, "batch_weight"):
-            raise NotImplementedError(f"constraint {name}: {type(loss).__name__} with weight grids on a SPINN grid: the reference "
-                                      "broadcasts its per-sample errors against the weight column of a batch, which a grid has not")
-        outputs = {}
-        for k, v in vals.items():
-            v = v._as_sym() if hasattr(v, "_as_sym") else v
-            outputs[k] = v if isinstance(v, graph.Sym) else graph._lift(v)
-        losses = [dict(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None, area=None,
-                       scale=1.0, kind=getattr(loss, "term_kind", 0), causal=(k if getattr(loss, "causal", None) else None),
-                       periodic=bool(getattr(loss, "periodic", False))) for k in label_keys]
-        jet = JetTable(self.model)
-        try:
-            low = graph.lower(outputs, losses, extra_outputs, jet=jet)
-        except NotImplementedError as e:
-            raise NotImplementedError(f"constraint {name}: {e}") from None
-        return SpinnJetConstraint(name, self.model, low, jet, label_keys,
-                                  [(lambda total, k=k: loss.term_scale(k, total)) for k in label_keys], self.device,
-                                  self.world_size, self.rank)
-
-    def _compile_constraint(self, name: str, cst) -> CompiledConstraint:
-        if self._is_spinn:
+    def _compile_constraint(self, name: str, cst):
+        if hasattr(self.engine, "compile_constraint"):
             self._static[name] = False
-            return self._compile_spinn_constraint(name, cst)
-        if self._is_operator:
-            from ..operator_engine import OperatorConstraint
-
-            ds = getattr(cst.data_loader, "dataset", cst.data_loader)
-            self._static[name] = False
-            bsz = getattr(getattr(cst.data_loader, "batch_sampler", None), "batch_size", 0) or 0
-            return OperatorConstraint(name, self.model, cst.output_expr, cst.loss, self.device, list(ds.label_keys), bsz)
+            return self.engine.compile_constraint(name, cst, self.device, self.world_size, self.rank)
         ds = getattr(cst.data_loader, "dataset", cst.data_loader)
         if getattr(ds, "shard_in_engine", False) and self.world_size > 1:
             raise NotImplementedError(f"constraint {name}: 'shard_in_engine' datasets are only sharded by the SPINN engine")
@@ -330,15 +250,15 @@ class Solver:
             # the expressions are not a per-point program (arithmetic on row windows, tensor methods that reduce over the
             # batch, control flow on values that change every step, a derivative set beyond the instantiated stream sets
             # ...): refused with the reason -- there is no op-by-op fallback.  The other ranks are waiting in the collective
-            # of _check_trace_decisions: take part in it (it raises there as well), then raise the reason of this rank
-            self._check_trace_decisions(name, None, f"{type(e).__name__}: {e}")
+            # of check_trace_decisions: take part in it (it raises there as well), then raise the reason of this rank
+            check_trace_decisions(name, None, self.world_size, f"{type(e).__name__}: {e}")
             raise NotImplementedError(f"constraint {name}: not lowerable to the fused HIP kernels ({type(e).__name__}: {e})") from e
         if name in self._ragged and (cc.low.reductions or cc.low.couplings):
             raise NotImplementedError(f"constraint {name}: batch reductions / couplings over ragged data-parallel shards (the sampler's "
                                       "wrap-around duplicates would be counted twice); make the sample count a multiple of the ranks")
         if cc.specialised_to:
             logger.info(f"constraint {name}: traced for the values of its (fixed) batch: {', '.join(cc.specialised_to)}")
-        self._check_trace_decisions(name, cc)
+        check_trace_decisions(name, cc, self.world_size)
         if first is not None:
             inp, lab, w = first
             cc.bind(inp, lab, self._shard_weights(name, cst, lab, w))
@@ -371,6 +291,7 @@ class Solver:
         self.global_step = self.best_metric["epoch"] * self.iters_per_epoch
         start_epoch = self.best_metric["epoch"] + 1
         csts = list(self._compiled.values())
+        eng_csts = [c.step_obj for c in csts]  # what the engine's step takes for each constraint
         if getattr(self.loss_aggregator, "per_loss_grad", False):
             self._apply_loss_weights()
         total_batch_size = sum(c.batch_size for c in csts)
@@ -381,12 +302,8 @@ class Solver:
                 for name, cc in self._compiled.items():
                     if not self._static[name]:
                         inp, lab, w = next(self.constraint[name].data_iter)
-                        if self._is_spinn:
-                            cc.bind(inp, lab, w)
-                        else:
-                            cc.bind(inp, lab, self._shard_weights(name, self.constraint[name], lab, w))
+                        cc.bind(inp, lab, self._shard_weights(name, self.constraint[name], lab, w))
                 reader_cost = time.perf_counter() - reader_tic
-                eng_csts = csts if (self._is_spinn or self._is_operator) else [c.fused for c in csts]
                 gscale = (1.0 / self.world_size) if (self.engine.dp_reduce == "mean" and self.world_size > 1) else 1.0
                 if getattr(self.optimizer, "is_lbfgs", False):
                     # train_LBFGS_epoch_func (solver/train.py:216-315): the optimizer re-evaluates loss + gradient
@@ -519,56 +436,21 @@ class Solver:
         if self._reparam:
             self.model.materialize()
 
-    def _check_trace_decisions(self, name: str, cc, failure: Optional[str] = None) -> None:
-        """Python control flow on the values of a fixed batch is followed at trace time (graph.batch_values).  Under data
-        parallelism every rank traces on ITS shard: the ranks must end up with the SAME program (residual program, loss terms,
-        derivative streams), otherwise they would train different programs against one all-reduced gradient without anybody
-        noticing (the reference evaluates the user's function on each rank's tensors every step, utils/expression.py:96-102, so
-        there a rank-dependent branch is at least visible in the loss).  A collective: every rank calls it for every
-        constraint, in the same order."""
-        import zlib
-
-        dist = torch.distributed
-        if self.world_size <= 1 or not dist.is_available() or not dist.is_initialized():
-            return
-        if cc is None:  # this rank's trace raised: say so to everybody instead of leaving them in the collective
-            mine = (None, None, [], failure or "trace failed")
-        else:
-            mine = (zlib.crc32(bytes(cc.fused.edesc)), repr(cc.fused.streams), list(cc.specialised_to), None)
-        everyone = [None] * dist.get_world_size()
-        dist.all_gather_object(everyone, mine)
-        failed = [(r, e[3]) for r, e in enumerate(everyone) if e[3] is not None]
-        if failed:
-            if cc is None:
-                return  # the caller raises this rank's own reason
-            raise NotImplementedError(f"constraint {name}: not lowerable on rank {failed[0][0]} ({failed[0][1]}); its shard takes "
-                                      "a path through the expressions that this rank's shard does not")
-        if any(e[:2] != everyone[0][:2] for e in everyone):
-            odd = next(r for r, e in enumerate(everyone) if e[:2] != everyone[0][:2])
-            msg = (f"constraint {name}: the expressions branch on values of the batch and ranks 0 and {odd} took different "
-                   f"branches (rank 0 asked {everyone[0][2]}; rank {odd} asked {everyone[odd][2]}): their programs differ")
-            if os.environ.get("PPSCI_RANK_SPECIFIC_TRACES", "0") == "1":
-                logger.warning(msg + " -- accepted (PPSCI_RANK_SPECIFIC_TRACES=1): every rank trains its own program")
-            else:
-                raise RuntimeError(msg + "; make the condition independent of the shard, or set PPSCI_RANK_SPECIFIC_TRACES=1 "
-                                         "to train rank-specific programs")
-
     def _step_in_one_launch(self, eng_csts, gscale: float) -> bool:
         """The whole iteration (train.py:82-184) as one launch per constraint, the optimizer step inside the last one,
         when nothing sits between the gradient and the update: one rank, plain Adam (no clipping / decay / learnable
         equation parameters), no re-parametrised weights, no gradient accumulation or per-loss gradients, and every
         constraint small enough for the one-launch kernel (engine.one_launch_ready).  False: nothing was done."""
         opt = self.optimizer
-        if (self.world_size != 1 or not eng_csts or self._reparam or self.update_freq > 1
-                or self._key_grads or type(opt).__name__ != "_AdamState"
-                or opt.grad_clip is not None or opt.l2 != 0.0 or opt.eq_store is not None
-                or not hasattr(self.engine, "one_launch_ready") or opt.model.flat_params.data_ptr() != self.engine.params.data_ptr()
-                or not self.engine.one_launch_ready(eng_csts)):
+        if (self.world_size != 1 or not eng_csts or self._reparam or self.update_freq > 1 or self._key_grads
+                or not hasattr(self.engine, "one_launch_ready") or not self.engine.one_launch_ready(eng_csts)):
+            return False
+        adam = fused_adam_args(opt, gscale, opt.t + 1)  # (asked last: the arguments are built only for a step that is taken)
+        if adam is None or opt.model.flat_params.data_ptr() != self.engine.params.data_ptr():
             return False
         self._materialize()
         opt.t += 1
-        self.engine.step_one_launch(eng_csts, dict(m=opt.m, v=opt.v, lr=opt.get_lr(), beta1=opt.beta1, beta2=opt.beta2,
-                                                   eps=opt.epsilon, grad_scale=gscale, t=opt.t))
+        self.engine.step_one_launch(eng_csts, adam)
         return True
 
     def _adam_behind_allreduce(self, eng_csts, gscale: float) -> bool:
@@ -576,12 +458,11 @@ class Solver:
         step's weight fragments in ONE launch behind the all-reduce (engine.apply_adam_fused) instead of the optimizer's own
         kernel + a weight-split launch.  False: nothing was done."""
         opt = self.optimizer
-        if (self.world_size == 1 or self._reparam or type(opt).__name__ != "_AdamState" or opt.grad_clip is not None or opt.l2 != 0.0
-                or opt.eq_store is not None or not hasattr(self.engine, "apply_adam_fused")
+        adam = None if (self.world_size == 1 or self._reparam) else fused_adam_args(opt, gscale, opt.t + 1)
+        if (adam is None or not hasattr(self.engine, "apply_adam_fused")
                 or opt.model.flat_params.data_ptr() != self.engine.params.data_ptr()):
             return False
-        if not self.engine.apply_adam_fused(eng_csts, dict(m=opt.m, v=opt.v, lr=opt.get_lr(), beta1=opt.beta1, beta2=opt.beta2,
-                                                           eps=opt.epsilon, grad_scale=gscale, t=opt.t + 1)):
+        if not self.engine.apply_adam_fused(eng_csts, adam):
             return False
         opt.t += 1
         return True
@@ -591,8 +472,8 @@ class Solver:
         partials of the 1x1 convolutions' weight gradients): one rank, plain Adam, nothing between the gradient and the update
         -- the sums and the update are ONE launch (hp.reduce_rows_multi_adam) instead of two.  False: nothing was done."""
         opt, eng = self.optimizer, self.engine
-        if (self.world_size != 1 or not hasattr(eng, "forward_backward_deferred") or type(opt).__name__ != "_AdamState"
-                or opt.grad_clip is not None or opt.l2 != 0.0 or opt.eq_store is not None or self.update_freq > 1 or self._reparam
+        if (self.world_size != 1 or not hasattr(eng, "forward_backward_deferred") or fused_adam_args(opt, gscale, opt.t + 1) is None
+                or self.update_freq > 1 or self._reparam
                 or self._key_grads or os.environ.get("PPSCI_FUSED_REDUCE_ADAM", "1") == "0"
                 or opt.model.flat_params.data_ptr() != self.model.flat_params.data_ptr()):
             return False
@@ -607,7 +488,7 @@ class Solver:
         return self.model.pull_back(self.engine.grad) if self._reparam else self.engine.grad
 
     def _update_loss_weights(self, eng_csts):
-        if self._is_spinn or self._is_operator:
+        if not self.engine.per_key_pass:
             raise NotImplementedError("GradNorm / NTK need the fused PINN engine")
         saved = self.engine.grad.clone()
         saved_terms = [cc.fused.loss_terms.clone() for cc in self._compiled.values()]
@@ -628,7 +509,7 @@ class Solver:
     # ------------------------------------------------------------------ per-loss gradient matrix (PCGrad / Relobralo)
     def _check_grad_matrix_supported(self) -> None:
         name = type(self.loss_aggregator).__name__
-        if self._is_spinn or self._is_operator:
+        if not self.engine.per_key_pass:
             raise NotImplementedError(f"{name} needs the fused PINN engine (one masked pass per loss key), as GradNorm / NTK do; "
                                       "SPINN and operator models have no masked pass")
         if getattr(self.optimizer, "is_lbfgs", False):
@@ -718,11 +599,9 @@ class Solver:
         losses = None
         if self.world_size > 1:
             losses, order, rho = self._share_over_ranks(b, keys, order, rho, gscale)
-        adam = None
-        if (type(opt).__name__ == "_AdamState" and opt.grad_clip is None and opt.l2 == 0.0 and opt.eq_store is None
-                and opt.model.flat_params.numel() == g0.numel()):
-            adam = dict(m=opt.m, v=opt.v, lr=opt.get_lr(), beta1=opt.beta1, beta2=opt.beta2, eps=opt.epsilon,
-                        grad_scale=gscale, t=opt.t + 1)
+        adam = fused_adam_args(opt, gscale, opt.t + 1)
+        if adam is not None and opt.model.flat_params.numel() != g0.numel():
+            adam = None
         params = opt.model.flat_params if adam is not None else None
         if agg.device_rule:
             hp.grad_surgery(b["G"], b["gram"], b["ws"], order, b["coef"], b["w"])
@@ -746,20 +625,15 @@ class Solver:
         losses_all: Dict[str, float] = {}
         per_cst: Dict[str, float] = {}
         for name, cc in self._compiled.items():
-            if self._is_operator:
-                vals = cc.losses()  # keys are whatever the loss returns (FunctionalLoss), not the label keys
-                keys = list(vals.keys())
-            else:
-                vals = cc.losses() if self._is_spinn else cc.fused.losses()
-                keys = cc.label_keys
-                if getattr(self.loss_aggregator, "per_loss_grad", False) and hasattr(cc, "_base_scales"):
-                    # the kernels applied the aggregator's weights through the residual scales: report raw terms
-                    order = self._loss_key_order()
-                    vals = {k: vals[k] / max(float(self.loss_aggregator.weight[order.index(k)]), 1e-30) for k in keys}
+            vals = cc.losses()  # (an operator constraint's keys are whatever its loss returns, not the label keys)
+            if getattr(self.loss_aggregator, "per_loss_grad", False) and hasattr(cc, "_base_scales"):
+                # the kernels applied the aggregator's weights through the residual scales: report raw terms
+                order = self._loss_key_order()
+                vals = {k: v / max(float(self.loss_aggregator.weight[order.index(k)]), 1e-30) for k, v in vals.items()}
             per_cst[name] = 0.0
-            for k in keys:
-                per_cst[name] += vals[k]
-                losses_all[k] = losses_all.get(k, 0.0) + vals[k]
+            for k, v in vals.items():
+                per_cst[name] += v
+                losses_all[k] = losses_all.get(k, 0.0) + v
         if getattr(self.loss_aggregator, "grad_matrix", False) and not self.loss_aggregator.device_rule:
             total = float(self._mtl_total)  # Relobralo: sum_k lambda_k L_k of the step (its __call__ advances the state)
         else:
@@ -797,45 +671,54 @@ class Solver:
             raise ValueError("Solver.eval needs at least one validator")
         target = float("inf")
         group: Dict[str, Dict[str, float]] = {}
-        if self._is_operator:
-            return self._eval_operator(epoch_id)
         for vname, val in self.validator.items():
-            ds = getattr(val.data_loader, "dataset", val.data_loader)
-            outs: Dict[str, list] = {}
-            labs: Dict[str, list] = {}
-            loss_sum: Dict[str, float] = {}
-            nb = 0
-            for (inp, lab, w) in val.data_loader:
-                bsz = len(next(iter(inp.values())))
-                key = (vname, bsz)
-                if key not in self._compiled_val:
-                    self._compiled_val[key] = CompiledConstraint(
-                        vname, self.model, val.output_expr, list(ds.input_keys), list(ds.label_keys),
-                        list((ds.weight or {}).keys()), val.loss, bsz, bsz, self.device, train=False, want_values=True,
-                        extra_parameters=self._extra_parameters())
-                cc = self._compiled_val[key]
-                cc.bind(inp, lab, w)
-                cc.fused.forward(self.model.materialize(), False)
-                vals = cc.values()
-                lv = cc.fused.losses()
-                for k in cc.label_keys:
-                    outs.setdefault(k, []).append(vals[k].clone())
-                    labs.setdefault(k, []).append(torch.as_tensor(np.asarray(lab[k], dtype=np.float32)).to(self.device).view(-1, 1))
-                    loss_sum[k] = loss_sum.get(k, 0.0) + lv[k]
-                nb += 1
-            n_total = len(ds) if hasattr(ds, "__len__") and not getattr(ds, "is_iterable", False) else None
-            all_out = {k: self._gather_eval(torch.cat(v, 0), n_total) for k, v in outs.items()}
-            all_lab = {k: self._gather_eval(torch.cat(v, 0), n_total) for k, v in labs.items()}
-            group[vname] = {}
-            for mname, metric in (val.metric or {}).items():
-                res = metric(all_out, all_lab)
-                for k, v in res.items():
-                    group[vname][f"{mname}.{k}"] = _metric_value(v)
-            msg = ", ".join(f"{k}: {v:.5f}" for k, v in group[vname].items())
-            logger.info(f"[Eval][Epoch {epoch_id}][{vname}] loss: {sum(loss_sum.values()) / max(nb, 1):.5f}, {msg}")
+            run = getattr(self.engine, "eval_validator", None)
+            outs, labs, loss = run(val, self.device) if run else self._eval_validator(vname, val)
+            group[vname] = self._eval_metrics(epoch_id, vname, val, outs, labs, loss)
             if group[vname] and target == float("inf"):
                 target = float(next(iter(group[vname].values())))  # first metric of the first validator
         return target, group
+
+    def _eval_validator(self, vname: str, val):
+        """One validator on the compiled forward: its values and labels per key ({key: [batches]}) and the mean batch loss."""
+        ds = getattr(val.data_loader, "dataset", val.data_loader)
+        outs: Dict[str, list] = {}
+        labs: Dict[str, list] = {}
+        loss_sum: Dict[str, float] = {}
+        nb = 0
+        for (inp, lab, w) in val.data_loader:
+            bsz = len(next(iter(inp.values())))
+            key = (vname, bsz)
+            if key not in self._compiled_val:
+                self._compiled_val[key] = CompiledConstraint(
+                    vname, self.model, val.output_expr, list(ds.input_keys), list(ds.label_keys),
+                    list((ds.weight or {}).keys()), val.loss, bsz, bsz, self.device, train=False, want_values=True,
+                    extra_parameters=self._extra_parameters())
+            cc = self._compiled_val[key]
+            cc.bind(inp, lab, w)
+            cc.fused.forward(self.model.materialize(), False)
+            vals = cc.values()
+            lv = cc.fused.losses()
+            for k in cc.label_keys:
+                outs.setdefault(k, []).append(vals[k].clone())
+                labs.setdefault(k, []).append(torch.as_tensor(np.asarray(lab[k], dtype=np.float32)).to(self.device).view(-1, 1))
+                loss_sum[k] = loss_sum.get(k, 0.0) + lv[k]
+            nb += 1
+        return outs, labs, sum(loss_sum.values()) / max(nb, 1)
+
+    def _eval_metrics(self, epoch_id: int, vname: str, val, outs, labs, loss: float) -> Dict[str, float]:
+        """The end of every validator's evaluation: all ranks' values and labels in dataset order, the metrics, the log line."""
+        ds = getattr(val.data_loader, "dataset", val.data_loader)
+        n_total = len(ds) if hasattr(ds, "__len__") and not getattr(ds, "is_iterable", False) else None
+        all_out = {k: self._gather_eval(torch.cat(v, 0), n_total) for k, v in outs.items()}
+        all_lab = {k: self._gather_eval(torch.cat(v, 0), n_total) for k, v in labs.items()}
+        res: Dict[str, float] = {}
+        for mname, metric in (val.metric or {}).items():
+            for k, v in metric(all_out, all_lab).items():
+                res[f"{mname}.{k}"] = _metric_value(v)
+        msg = ", ".join(f"{k}: {v:.5f}" for k, v in res.items())
+        logger.info(f"[Eval][Epoch {epoch_id}][{vname}] loss: {loss:.5f}, {msg}")
+        return res
 
     def _gather_eval(self, local: torch.Tensor, n_total: Optional[int]) -> torch.Tensor:
         """All ranks' shards in DATASET order, without the sampler's wrap-around padding (eval.py:154-161 truncates
@@ -847,85 +730,13 @@ class Solver:
         full = full.view(self.world_size, nl, *local.shape[1:]).transpose(0, 1).reshape(nl * self.world_size, *local.shape[1:])
         return full if n_total is None else full[:n_total]
 
-    def _eval_operator(self, epoch_id: int):
-        """eval.py _eval_by_dataset for models evaluated through torch (FNO): whole-dataset metrics."""
-        from ..operator_engine import _to_dev
-
-        target = float("inf")
-        group: Dict[str, Dict[str, float]] = {}
-        self.model.eval()
-        for vname, val in self.validator.items():
-            outs: Dict[str, list] = {}
-            labs: Dict[str, list] = {}
-            loss_sum, nb = 0.0, 0
-            with torch.no_grad():
-                for (inp, lab, w) in val.data_loader:
-                    inp_d, lab_d, w_d = _to_dev(inp, self.device), _to_dev(lab, self.device), _to_dev(w, self.device)
-                    out = self.model(inp_d)
-                    data = {**inp_d, **out}
-                    vals = {k: f(data) for k, f in val.output_expr.items()}
-                    loss_sum += float(sum(val.loss(vals, lab_d, w_d).values()))
-                    nb += 1
-                    for k in vals:
-                        outs.setdefault(k, []).append(vals[k])
-                    for k in lab_d:
-                        labs.setdefault(k, []).append(lab_d[k])
-            ds = getattr(val.data_loader, "dataset", val.data_loader)
-            n_total = len(ds) if hasattr(ds, "__len__") and not getattr(ds, "is_iterable", False) else None
-            all_out = {k: self._gather_eval(torch.cat(v, 0), n_total) for k, v in outs.items()}
-            all_lab = {k: self._gather_eval(torch.cat(v, 0), n_total) for k, v in labs.items()}
-            group[vname] = {}
-            for mname, metric in (val.metric or {}).items():
-                for k, v in metric(all_out, all_lab).items():
-                    group[vname][f"{mname}.{k}"] = _metric_value(v)
-            msg = ", ".join(f"{k}: {v:.5f}" for k, v in group[vname].items())
-            logger.info(f"[Eval][Epoch {epoch_id}][{vname}] loss: {loss_sum / max(nb, 1):.5f}, {msg}")
-            if group[vname] and target == float("inf"):
-                target = float(next(iter(group[vname].values())))
-        self.model.train()
-        return target, group
-
     # ------------------------------------------------------------------ prediction
     def predict(self, input_dict: Dict[str, Union[np.ndarray, torch.Tensor]], expr_dict: Optional[Dict[str, Callable]] = None,
                 batch_size: Optional[int] = 64, no_grad: bool = True, return_numpy: bool = False):
         """solver.py:729-872.  With world_size > 1 the points are rank-strided (v[rank::world]) and the
         gathered result is restored to the input order, like the reference (:793-797, :847-855)."""
-        if self._is_operator:
-            from ..operator_engine import _to_dev
-
-            n = len(next(iter(input_dict.values())))
-            bs = n if batch_size is None else batch_size
-            exprs = expr_dict if expr_dict is not None else {k: (lambda out, k=k: out[k]) for k in self.model.output_keys}
-            res: Dict[str, list] = {k: [] for k in exprs}
-            with torch.no_grad():
-                for s0 in range(0, n, bs):
-                    chunk = _to_dev({k: v[s0:s0 + bs] for k, v in input_dict.items()}, self.device)
-                    data = {**chunk, **self.model(chunk)}
-                    for k, f in exprs.items():
-                        res[k].append(f(data))
-            pred = {k: torch.cat(v, 0) for k, v in res.items()}
-            return {k: v.cpu().numpy() for k, v in pred.items()} if return_numpy else pred
-        if self._is_spinn:  # tensor-product grid of the three coordinate vectors (helmholtz3d.py:205-213)
-            out = self.model(input_dict)
-            if expr_dict is not None:
-                # the expressions on the same grid through the general path: forward sweep, stream contraction and the epilogue's
-                # residual rows (no adjoint), as [nx,ny,nz,1] arrays next to the model outputs
-                from ..graph import Sym
-
-                ck = (id(expr_dict), "spinn")
-                if ck not in self._predict_cache:
-                    data = {k: Sym.input(k) for k in self.model.input_keys}
-                    data.update(self.model(data))
-                    vals = {k: f(data) for k, f in expr_dict.items()}
-                    autodiff.clear()
-                    # (the dict is kept with its constraint: its id stays unique for as long as the cache entry lives)
-                    self._predict_cache[ck] = (self._spinn_jet_constraint("predict", vals, [], [], None, tuple(expr_dict)), expr_dict)
-                cc = self._predict_cache[ck][0]
-                cc.world = 1  # every rank evaluates the grid it is given
-                cc.bind({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in input_dict.items()}, {})
-                cc.forward(False, False, want_resid=True)
-                out = dict(out, **{k: v.clone() for k, v in cc.values().items()})
-            return {k: v.detach().cpu().numpy() for k, v in out.items()} if return_numpy else out
+        if hasattr(self.engine, "predict"):
+            return self.engine.predict(input_dict, expr_dict, batch_size, return_numpy, self.device)
         n = len(next(iter(input_dict.values())))
         batch_size = n if batch_size is None else batch_size
         keys = list(input_dict.keys())
@@ -1016,15 +827,11 @@ class Solver:
     @staticmethod
     def no_grad_context_manager(enable: bool):
         """solver.py:933-951.  The compiled forward never records a tape; the context only matters for user code on torch tensors."""
-        import contextlib
-
         return torch.no_grad() if enable else contextlib.nullcontext()
 
     @staticmethod
     def autocast_context_manager(enable: bool, level: str = "O1"):
         """solver.py:913-931: AMP is not available on the fused path (fp32 only)."""
-        import contextlib
-
         if enable:
             raise NotImplementedError("AMP is not available on the fused HIP path (fp32 only)")
         return contextlib.nullcontext()

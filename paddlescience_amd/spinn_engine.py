@@ -3,7 +3,8 @@
 then one fixed-order reduction per branch into the flat gradient, one all-reduce, one fused Adam.
 Counterpart of the generic engine.py for BASELINE config 5 (examples/spinn/helmholtz3d.py of the
 reference: one PDE constraint on the nc^3 grid + six boundary faces).  Data parallelism shards the
-points of one axis rank-strided (each rank owns an [nx/W, ny, nz] slab of the interior grid); branch nets are replicated."""
+points of one axis rank-strided (each rank owns an [nx/W, ny, nz] slab of the interior grid); branch nets are replicated.
+SpinnEngine and its two constraint kinds implement the engine contract stated in engine.py's docstring."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,11 +14,41 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import autodiff, graph
 from . import hotpath as hp
 import os
 
+from .arch.spinn import GridLinear, JetTable
+from .compile import LABEL_PREFIX, WEIGHT_PREFIX
 from .engine import StepGraph, run_on_streams
 from .hotpath import _p, _stream_ptr
+
+
+def _fp(a):
+    """What bind() takes for "the same array as last time": the object and three sampled values."""
+    f = np.asarray(a).reshape(-1)
+    n = f.shape[0]
+    return (id(a), n, float(f[0]), float(f[n // 2]), float(f[n - 1])) if n else (id(a), 0)
+
+
+def _alloc_branches(c, shape) -> None:
+    """Both constraint kinds' buffers for the three branch nets: points, factors, their adjoints, the stash, the gradient rows
+    (one per 16-point tile on the MFMA tile kernel of the reverse sweep, one per point otherwise).  With equal point counts the
+    rows interleave as [n][3][P]: one reduce_rows(n, 3P) sums all three into the flat gradient (branch b: grad[bP:(b+1)P])."""
+    m = c.model
+    R, P = m.spec.R, m.branch_params
+    f32 = dict(dtype=torch.float32, device=c.device)
+    c.x = [torch.zeros(n, **f32) for n in shape]
+    c.F = [torch.zeros((3, n, R), **f32) for n in shape]
+    c.Fbar = [torch.zeros((3, n, R), **f32) for n in shape]
+    c.stash = [torch.zeros(int(L.lib().ppsci_modmlp_stash_floats(C.byref(m.spec.desc), n)), **f32) for n in shape]
+    grows = [int(L.lib().ppsci_modmlp_bwd_rows(C.byref(m.spec.desc), n)) for n in shape]
+    c.gjoint = len(set(shape)) == 1
+    if c.gjoint:
+        c.gpart_all = torch.zeros((grows[0], 3 * P), **f32)
+        c.gpart = [c.gpart_all.view(-1)[b * P:] for b in range(3)]  # row 0 of branch b; rows are 3P apart
+    else:
+        c.gpart = [torch.zeros((r, P), **f32) for r in grows]
 
 
 class SpinnConstraint:
@@ -38,22 +69,9 @@ class SpinnConstraint:
         self._version += 1
         self._last_ids, self._uploaded = [None] * 4, [None] * 4
         nx, ny, nz = shape
-        R, P = m.spec.R, m.branch_params
+        R = m.spec.R
         f32 = dict(dtype=torch.float32, device=dev)
-        self.x = [torch.zeros(n, **f32) for n in shape]
-        self.F = [torch.zeros((3, n, R), **f32) for n in shape]
-        self.Fbar = [torch.zeros((3, n, R), **f32) for n in shape]
-        self.stash = [torch.zeros(int(L.lib().ppsci_modmlp_stash_floats(C.byref(m.spec.desc), n)), **f32) for n in shape]
-        # per-point gradient rows of the three branch nets: with equal point counts they interleave as [n][3][P], so that one
-        # reduce_rows(n, 3P) call sums all three into the flat gradient (branch b's parameters are grad[bP:(b+1)P])
-        # (rows: one per 16-point tile on the MFMA tile kernel of the reverse sweep, one per point otherwise)
-        grows = [int(L.lib().ppsci_modmlp_bwd_rows(C.byref(m.spec.desc), n)) for n in shape]
-        self.gjoint = len(set(shape)) == 1
-        if self.gjoint:
-            self.gpart_all = torch.zeros((grows[0], 3 * P), **f32)
-            self.gpart = [self.gpart_all.view(-1)[b * P:] for b in range(3)]  # row 0 of branch b; rows are 3P apart
-        else:
-            self.gpart = [torch.zeros((r, P), **f32) for r in grows]
+        _alloc_branches(self, shape)
         total = nx * ny * nz
         self.label = torch.zeros(total, **f32)
         self.gadj = torch.zeros(total, **f32)
@@ -67,6 +85,7 @@ class SpinnConstraint:
         self.loss_term = torch.zeros(1, **f32)
 
     lcols = 1  # columns of `lpart` / entries of `loss_term` (one loss key)
+    step_obj = property(lambda self: self)
 
     @property
     def scale_key(self):  # what a captured step holds by value besides the buffers
@@ -102,11 +121,6 @@ class SpinnConstraint:
         # The reference re-uploads every iteration.  Here an array is uploaded only when it changed: the same
         # object with the same sampled values is taken as unchanged (in-place edits that keep first / middle /
         # last are not seen); a new object is compared in full with a private copy of what was uploaded last.
-        def _fp(a):
-            f = np.asarray(a).reshape(-1)
-            n = f.shape[0]
-            return (id(a), n, float(f[0]), float(f[n // 2]), float(f[n - 1])) if n else (id(a), 0)
-
         srcs = [input[k] for k in keys] + [label[self.label_key]]
         vals = arrs + [lab.reshape(-1)]
         dsts = list(self.x) + [self.label]
@@ -174,8 +188,6 @@ class SpinnJetConstraint:
     key and `loss_term` one entry per key."""
 
     def __init__(self, name: str, model, low, jet, label_keys: Sequence[str], scale_fns, device, world: int = 1, rank: int = 0):
-        from .compile import LABEL_PREFIX, WEIGHT_PREFIX
-
         self.name, self.model, self.low, self.jet = name, model, low, jet
         self.label_keys = list(label_keys)
         self.label_key = self.label_keys[0] if self.label_keys else None
@@ -200,6 +212,8 @@ class SpinnJetConstraint:
         self._scales = None
         self.edesc = None
 
+    step_obj = property(lambda self: self)
+
     @property
     def lcols(self) -> int:
         return len(self.program.res)
@@ -213,21 +227,11 @@ class SpinnJetConstraint:
         self.shape = tuple(shape)
         self._version += 1
         self._last_ids, self._uploaded = {}, {}
-        R, P = m.spec.R, m.branch_params
+        R = m.spec.R
         f32 = dict(dtype=torch.float32, device=dev)
         total = shape[0] * shape[1] * shape[2]
         nq = len(self.jet.orders)
-        self.x = [torch.zeros(n, **f32) for n in shape]
-        self.F = [torch.zeros((3, n, R), **f32) for n in shape]
-        self.Fbar = [torch.zeros((3, n, R), **f32) for n in shape]
-        self.stash = [torch.zeros(int(L.lib().ppsci_modmlp_stash_floats(C.byref(m.spec.desc), n)), **f32) for n in shape]
-        grows = [int(L.lib().ppsci_modmlp_bwd_rows(C.byref(m.spec.desc), n)) for n in shape]
-        self.gjoint = len(set(shape)) == 1
-        if self.gjoint:
-            self.gpart_all = torch.zeros((grows[0], 3 * P), **f32)
-            self.gpart = [self.gpart_all.view(-1)[b * P:] for b in range(3)]
-        else:
-            self.gpart = [torch.zeros((r, P), **f32) for r in grows]
+        _alloc_branches(self, shape)
         self.jdesc = L.SpinnJetDesc()
         self.jdesc.n[0], self.jdesc.n[1], self.jdesc.n[2] = shape
         self.jdesc.rank, self.jdesc.nq = R, nq
@@ -279,11 +283,6 @@ class SpinnJetConstraint:
         if self.shape != shape:
             self._alloc(shape)
 
-        def _fp(a):
-            f = np.asarray(a).reshape(-1)
-            n = f.shape[0]
-            return (id(a), n, float(f[0]), float(f[n // 2]), float(f[n - 1])) if n else (id(a), 0)
-
         def upload(slot, src, make, dst):
             """`make()` -> `dst` unless `src` is unchanged since the last upload into `slot` (SpinnConstraint.bind's rule)."""
             fp = _fp(src)
@@ -317,9 +316,7 @@ class SpinnJetConstraint:
             self.edesc = self.program.build()
 
     def _epilogue_args(self):
-        any_x = self.x[0]
-        inputs = [self.xgrid.get(j, any_x) for j in range(len(self.model.input_keys))]
-        return inputs
+        return [self.xgrid.get(j, self.x[0]) for j in range(len(self.model.input_keys))]
 
     def forward(self, train: bool, reduce_loss: bool = True, want_resid: bool = False):
         m, lib = self.model, L.lib()
@@ -358,8 +355,36 @@ class SpinnJetConstraint:
         return {k: self.resid[i].view(*self.shape, 1) for i, k in enumerate(self.low.loss_keys)}
 
 
+def jet_constraint(name, model, vals, label_keys, weight_keys, loss, device, world=1, rank=0, extra_outputs=()):
+    """Lowers traced SPINN expressions with graph.lower (the program builder of every other model) on a stream table of
+    per-axis derivative orders."""
+    if len(label_keys) + len(extra_outputs) > L.MAX_RES:
+        raise NotImplementedError(f"constraint {name}: {len(label_keys) + len(extra_outputs)} expression keys; one epilogue "
+                                  f"program holds {L.MAX_RES} (PPSCI_MAX_RES)")
+    if weight_keys and hasattr(loss, "batch_weight"):
+        raise NotImplementedError(f"constraint {name}: {type(loss).__name__} with weight grids on a SPINN grid: the reference "
+                                  "broadcasts its per-sample errors against the weight column of a batch, which a grid has not")
+    outputs = {}
+    for k, v in vals.items():
+        v = v._as_sym() if hasattr(v, "_as_sym") else v
+        outputs[k] = v if isinstance(v, graph.Sym) else graph._lift(v)
+    losses = [dict(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None, area=None,
+                   scale=1.0, kind=getattr(loss, "term_kind", 0), causal=(k if getattr(loss, "causal", None) else None),
+                   periodic=bool(getattr(loss, "periodic", False))) for k in label_keys]
+    jet = JetTable(model)
+    try:
+        low = graph.lower(outputs, losses, extra_outputs, jet=jet)
+    except NotImplementedError as e:
+        raise NotImplementedError(f"constraint {name}: {e}") from None
+    return SpinnJetConstraint(name, model, low, jet, label_keys, [(lambda total, k=k: loss.term_scale(k, total)) for k in label_keys],
+                              device, world, rank)
+
+
 class SpinnEngine:
+    per_key_pass = False
+
     def __init__(self, model):
+        self._predict_cache: Dict[int, tuple] = {}
         self.model = model
         self.grad = torch.zeros_like(model.flat_params)
         self.world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
@@ -433,6 +458,57 @@ class SpinnEngine:
     def invalidate_graphs(self) -> None:
         self._step_graph.clear()
 
-    def allreduce(self):
+    def allreduce(self, buf: Optional[torch.Tensor] = None):
         if self.world > 1:
-            torch.distributed.all_reduce(self.grad, op=torch.distributed.ReduceOp.SUM)
+            torch.distributed.all_reduce(self.grad if buf is None else buf, op=torch.distributed.ReduceOp.SUM)
+
+
+    def compile_constraint(self, name: str, cst, device, world: int = 1, rank: int = 0):
+        """A user constraint on a separable net.  One residual that is a linear form of {u, u_xx, u_yy, u_zz} without weights keeps
+        the four-coefficient grid kernels (arch.spinn.GridLinear -> SpinnConstraint); everything else -- several keys, weight grids,
+        non-linear residuals, first and mixed derivatives -- is lowered to an epilogue program over the derivative streams it
+        reads (SpinnJetConstraint).  PPSCI_SPINN_JET=1 sends a linear form down the general path too (A/B timing, tests)."""
+        model = self.model
+        ds = getattr(cst.data_loader, "dataset", cst.data_loader)
+        label_keys = list(ds.label_keys)
+        if hasattr(ds, "weight_fn"):  # ContinuousNamedArrayDataset
+            w0 = ds.weight_fn(ds.input_fn()) if callable(ds.weight_fn) else None
+            weight_keys = list(w0.keys()) if w0 else []
+        else:
+            weight_keys = list((getattr(ds, "weight", None) or {}).keys())
+        data = {k: graph.Sym.input(k) for k in model.input_keys}
+        data.update(model(data))
+        vals = {k: (cst.output_expr[k](data) if k in cst.output_expr else data[k]) for k in label_keys}
+        autodiff.clear()
+        loss = cst.loss
+        key = label_keys[0] if label_keys else None
+        linear = (len(label_keys) == 1 and not weight_keys and isinstance(vals[key], GridLinear)
+                  and getattr(loss, "term_kind", 0) == 0 and os.environ.get("PPSCI_SPINN_JET", "0") != "1")
+        if linear:
+            sc = SpinnConstraint(name, model, vals[key].c, key, lambda total, k=key: loss.term_scale(k, total), device, world, rank)
+        else:
+            sc = jet_constraint(name, model, vals, label_keys, weight_keys, loss, device, world, rank)
+        sc.batch_size = 0
+        sc.label_keys = label_keys
+        return sc
+
+    def predict(self, input_dict, expr_dict, batch_size, return_numpy: bool, device):
+        """The model on the tensor-product grid of the coordinate vectors (helmholtz3d.py:205-213; every rank: the grid it is given)
+        and `expr_dict` on the same grid through the general path (forward sweep, stream contraction, the epilogue's residual
+        rows, no adjoint), as [nx,ny,nz,1] arrays next to the model outputs."""
+        out = self.model(input_dict)
+        if expr_dict is not None:
+            ck = id(expr_dict)
+            if ck not in self._predict_cache:
+                data = {k: graph.Sym.input(k) for k in self.model.input_keys}
+                data.update(self.model(data))
+                vals = {k: f(data) for k, f in expr_dict.items()}
+                autodiff.clear()
+                # (the dict is kept with its constraint: its id stays unique for as long as the cache entry lives)
+                self._predict_cache[ck] = (jet_constraint("predict", self.model, vals, [], [], None, device,
+                                                          extra_outputs=tuple(expr_dict)), expr_dict)
+            cc = self._predict_cache[ck][0]
+            cc.bind({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in input_dict.items()}, {})
+            cc.forward(False, False, want_resid=True)
+            out = dict(out, **{k: v.clone() for k, v in cc.values().items()})
+        return {k: v.detach().cpu().numpy() for k, v in out.items()} if return_numpy else out

@@ -217,7 +217,7 @@ def main_iterable(outdir):
 
 def main_branch(outdir):
     """Python control flow on the values of a fixed batch, under two ranks whose shards give DIFFERENT answers: refused on every
-    rank (solver.Solver._check_trace_decisions); a condition every shard answers alike is accepted."""
+    rank (compile.check_trace_decisions); a condition every shard answers alike is accepted."""
     import ppsci
     from paddlescience_amd import device
     from tests.emu import build_emu

@@ -161,7 +161,7 @@ def test_slab_sharding_sums_to_one_rank(dev, tmp_path):
     inp, lab, w = next(cst.data_iter)
     res = []
     for world, rank in ((1, 0), (2, 0), (2, 1)):
-        cc = solver._compile_spinn_constraint("PDE", cst)
+        cc = solver.engine.compile_constraint("PDE", cst, solver.device)
         cc.world, cc.rank = world, rank
         cc.bind(inp, lab, w)
         solver.engine.forward_backward([cc])
