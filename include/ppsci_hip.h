@@ -362,6 +362,13 @@ int ppsci_taylor_step_plan_set_scales(ppsci_step_plan* plan, const ppsci_epilogu
 int ppsci_taylor_step_run_main(ppsci_step_plan* plan, void* stream);
 void ppsci_taylor_step_plan_free(ppsci_step_plan* plan);
 int ppsci_taylor_step_plan_static(const ppsci_step_plan* plan, const char** name);
+/* kind 2, compile-time programs: nets whose shape has a shape-specialised instantiation of the fused tile kernel (raw inputs and
+ * outputs compile-time: csrc/taylor_fused.inc, D_RAW / M) run it when the plan requests none of U, Ubar, residual_out -- the
+ * same arithmetic in the same order with fewer scalar instructions around it.  0 keeps every plan on the generic kernel (tests
+ * and tools compare the two); default on.  Read when a launch is PLANNED.  _plan_specialised: 1 when the plan runs the
+ * shape-specialised kernel, else 0. */
+void ppsci_set_fused_specialised(int on);
+int ppsci_taylor_step_plan_specialised(const ppsci_step_plan* plan);
 int ppsci_taylor_step(const ppsci_mlp_desc* d, const ppsci_epilogue_desc* e, float* params, int64_t n_points,
                       const float* const* inputs_host, const float* const* aux_host, float* U, float* Ubar,
                       float* residual_out, void* stash, void* workspace, int64_t workspace_bytes, float* loss_terms,

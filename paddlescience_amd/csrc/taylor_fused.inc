@@ -41,6 +41,7 @@
 #define PPSCI_FUSED_LANE_BIAS(L, S, ACT, STATIC) ((L) * ((S) + 1) <= (((STATIC) && (ACT) == PPSCI_ACT_TANH) ? 20 : 12))
 #endif
 #define PPSCI_FUSED_EPI_SCRATCH ((PPSCI_MAX_RES + PPSCI_MAX_EPARAM) * 16)  // epi_finale's LDS (floats)
+#define PPSCI_FUSED_SPEC_TAB (64 + PPSCI_MAX_RES + PPSCI_MAX_DIRS * PPSCI_FUSED_MAX_IN)  // shape-specialised kernels: LDS table floats
 #define PPSCI_FUSED_MAX_IN 4  // raw inputs held in registers per lane (x, y, z, t); nets with more take the separate launches
 // x[j] for a runtime j out of the register array (a select chain: dynamic indexing would put the array into scratch)
 #define PPSCI_FUSED_XJ(x, j) ((j) == 0 ? (x)[0] : ((j) == 1 ? (x)[1] : ((j) == 2 ? (x)[2] : (x)[3])))
@@ -104,13 +105,34 @@ static inline long long ppsci_fused_floats(const ppsci_mlp_desc& d, const ppsci_
   return fl;
 }
 
+// LDS floats of one workgroup of a shape-specialised kernel (the kernel's carve-up with its compile-time shape): what a STATIC
+// plan never touches is left out -- the VM register file, `uls`, `rres` and all of the program tables but the constants and scales
+template <int NB, int LH, int N1, int N2, int D_RAW, int M>
+static constexpr long long ppsci_fused_floats_spec() {
+  constexpr int S = 1 + N1 + N2, HP = 16 * NB, pad4m = ((M + 3) / 4) * 4;
+  long long fl = 2LL * ((D_RAW + LH + M) * HP + pad4m);        // W0s Bs WLs BLs | gW0 gB gWL gBL
+  fl += 2LL * NB * M * S * PPSCI_TILE;                         // tin | red
+  fl += NB * D_RAW * PPSCI_TILE;                               // tinx
+  fl += PPSCI_FUSED_EPI_SCRATCH + PPSCI_MAX_RES * PPSCI_TILE;  // ered | lacc
+  fl += PPSCI_FUSED_SPEC_TAB;                                  // constants | scales | directions
+  fl += 2LL * S * NB * 3 * 64 * 2;                             // zx | hx
+  fl += PPSCI_MAX_DIRS * HP;                                   // dz0
+  return fl;
+}
+
 // STATIC: the kernel of plans whose residual program is a compile-time table (args.e.static_id > 0, epi_static.h) AND whose
 // inputs are all raw (no period embedding, no input streams: taylor_api.hip fill_step) -- it holds neither the VM nor the
 // interpreter (their registers, the parking of the stash around them, the barrier behind them) nor the general layer 0;
 // !STATIC: the program runs on the VM (pre-decoded) or on the interpreter, on wave 0.
-template <int NB, int LH, int N1, int N2, int ACT, bool STATIC, int ABL = 0>
+// D_RAW, M > 0 (shape-specialised, STATIC only): the number of raw inputs and of net outputs are compile-time -- the loops over
+// them, every offset of the LDS carve-up (ppsci_fused_floats_spec) and the guards of the optional outputs (U, dL/dU, residual
+// values: such plans take the D_RAW = M = 0 kernel) leave the tile loop, and with them the uniform values the compiler kept
+// alive for them across the loop in spilled SGPRs.  Same arithmetic, order, barriers and exchange layouts.
+template <int NB, int LH, int N1, int N2, int ACT, bool STATIC, int ABL = 0, int D_RAW = 0, int M = 0>
 __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args) {
   constexpr int S = 1 + N1 + N2;
+  constexpr bool SPEC = D_RAW > 0;
+  static_assert(!SPEC || (STATIC && M > 0 && D_RAW <= PPSCI_FUSED_MAX_IN), "shape-specialised kernels are STATIC kernels");
   constexpr int HP = 16 * NB;
   constexpr int W = NB;
   constexpr int L = LH;
@@ -122,9 +144,9 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, c = lane & 15;
-  const int H = a.d.width, m = a.d.d_out, d0 = a.q.d0, d_raw = a.d.d_raw;
+  const int H = a.d.width, m = SPEC ? M : a.d.d_out, d0 = SPEC ? D_RAW : a.q.d0, d_raw = SPEC ? D_RAW : a.d.d_raw;
   const int pad4m = ((m + 3) / 4) * 4;
-  const int n_instr = args.e.e.n_instr;
+  const int n_instr = SPEC ? 0 : args.e.e.n_instr;
 
   float* W0s = smem;
   float* Bs = W0s + d0 * HP;
@@ -136,14 +158,15 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   float* gBL = gWL + m * HP;
   float* tin = gBL + pad4m;                        // [W][m*S][16] dL/dU of the tile (the VM: copy 0; compile-time programs: copy `wave`)
   float* uls = tin + W * m * S * PPSCI_TILE;       // [m*S][16] U of the tile (pre-decoded programs with a VGPR register file)
-  float* tinx = uls + m * S * PPSCI_TILE;          // [W][d_raw][16] inputs of the tile as the residual program / reverse layer 0 read them
+  float* tinx = uls + (SPEC ? 0 : m * S * PPSCI_TILE);  // [W][d_raw][16] inputs of the tile as the residual program / reverse layer 0 read them
   float* red = tinx + W * d_raw * PPSCI_TILE;      // [W][m*S][16] last-linear partial sums
   float* ered = red + W * m * S * PPSCI_TILE;      // epi_finale scratch
   float* lacc = ered + PPSCI_FUSED_EPI_SCRATCH;    // [PPSCI_MAX_RES][16] loss sums of the VM lanes
   float* rf = lacc + PPSCI_MAX_RES * PPSCI_TILE;   // VM register file: values [n][16] | adjoints [n][16]
   unsigned* ftab = (unsigned*)(rf + 2 * n_instr * PPSCI_TILE);  // tables of the pre-decoded program (epi_fast_init)
   float* rres = (float*)(ftab + EPI_FAST_WORDS + PPSCI_MAX_RES);  // [PPSCI_MAX_RES][16] residual values of the tile
-  u32x2* zx = (u32x2*)(rres + PPSCI_MAX_RES * PPSCI_TILE);      // [S][NB][3][64] split planes (paired layout): zbar_l; forward: h of odd layers
+  // (SPEC: no uls / rf / rres; of the tables only the 64 constants, the PPSCI_MAX_RES scales and the N1 x D_RAW directions)
+  u32x2* zx = (u32x2*)(SPEC ? (float*)ftab + PPSCI_FUSED_SPEC_TAB : rres + PPSCI_MAX_RES * PPSCI_TILE);  // [S][NB][3][64] split planes (paired layout): zbar_l; forward: h of odd layers
   u32x2* hx = zx + S * NB * 3 * 64;                     // the same: h_{l-1};                             forward: h of even layers
   float* dz0 = (float*)(hx + S * NB * 3 * 64);  // [N1][HP]: z_0 of the first-derivative streams when every input is raw (below)
   f32x4* zsave = (f32x4*)hx;  // [L][S][64]: wave 0 parks its stash here while it runs the residual program (both exchange
@@ -170,7 +193,8 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   // of a first-derivative stream is sum_j W0[j][f] dirs[i][j], the same for every point; of a second-derivative stream, 0.
   // One table per launch instead of d_raw x N1 multiply-adds (and as many descriptor look-ups) per tile.
   bool raw_only = true;
-  for (int j = 0; j < d_raw; ++j) raw_only = raw_only && a.d.embed[j] == PPSCI_EMBED_NONE;
+  if constexpr (!SPEC)
+    for (int j = 0; j < d_raw; ++j) raw_only = raw_only && a.d.embed[j] == PPSCI_EMBED_NONE;
   if (raw_only)
     for (int idx = tid; idx < N1 * HP; idx += nthr) {
       const int i = idx / HP, f = idx - i * HP;
@@ -181,7 +205,11 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   const int nacc_small = (d0 + L + m) * HP + pad4m;  // gW0 .. gBL are contiguous
   for (int idx = tid; idx < nacc_small; idx += nthr) gW0[idx] = 0.f;
   for (int idx = tid; idx < PPSCI_MAX_RES * PPSCI_TILE; idx += nthr) lacc[idx] = 0.f;
-  if (args.e.fast != nullptr) epi_fast_init(args.e, ftab, rf + (lane & 15), PPSCI_TILE, tid, nthr, wave == 0 && lane < PPSCI_TILE);
+  if constexpr (SPEC) {
+    for (int k = tid; k < 64; k += nthr) ftab[k] = args.e.fast[192 + k];
+    for (int k = tid; k < PPSCI_MAX_RES; k += nthr) ftab[64 + k] = __builtin_bit_cast(unsigned, args.e.e.res[k].scale);
+    for (int k = tid; k < N1 * D_RAW; k += nthr) ((float*)ftab)[64 + PPSCI_MAX_RES + k] = a.d.dirs[k / D_RAW][k % D_RAW];
+  } else if (args.e.fast != nullptr) epi_fast_init(args.e, ftab, rf + (lane & 15), PPSCI_TILE, tid, nthr, wave == 0 && lane < PPSCI_TILE);
 
   // The raw inputs of a tile arrive in REGISTERS: every lane holds the (up to PPSCI_FUSED_MAX_IN) inputs of ITS point c,
   // requested during the previous tile's reverse sweep (an HBM round trip that nothing of that tile depends on).  Wave 0
@@ -199,10 +227,14 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   // compile-time residual programs (epi_static.h): the constants of the load table and the terms' scales, entry k in lane k
   const int static_id = STATIC ? args.e.static_id : 0;
   float st_cvals = 0.f, st_scales = 0.f;
-  if constexpr (STATIC) {
+  if constexpr (SPEC) {
+    st_cvals = __builtin_bit_cast(float, ftab[lane & 63]);
+    st_scales = __builtin_bit_cast(float, ftab[64 + (lane & (PPSCI_MAX_RES - 1))]);
+  } else if constexpr (STATIC) {
     st_cvals = __builtin_bit_cast(float, ftab[192 + (lane & 63)]);
     st_scales = __builtin_bit_cast(float, ftab[EPI_FAST_WORDS + (lane & (PPSCI_MAX_RES - 1))]);
   }
+  const float* const dirs_s = (const float*)ftab + 64 + PPSCI_MAX_RES;  // SPEC: [N1][D_RAW] directions (reverse layer 0)
 
   // running sums of Wbar_{l+1}[all input blocks ib][own output block], l = 0 .. L-2
   f32x4 wacc[L - 1][NB];
@@ -228,6 +260,11 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
     const int tile = a.tile0 + it * (int)gridDim.x + (int)blockIdx.x;  // uniform over the workgroup
     if (tile >= a.ntiles) break;
     PPSCI_FT(0)
+    // SPEC: the lane index is opaque once per tile -- the masks derived from it (c == 15, g == 0, lane < 16) are then one compare
+    // where they are used instead of SGPR pairs kept (spilled) across the whole loop
+    int lane_t = lane;
+    if constexpr (SPEC) PPSCI_OPAQUE(lane_t);
+    const int lane = lane_t, g = lane >> 4, c = lane & 15;
     // compile-time programs: every wave has its own copy of dL/dU and of the tile's inputs (no barrier between the sweeps)
     const float* tx = STATIC ? tinx + wave * (d_raw * PPSCI_TILE) : tinx;
     float* const tinw = STATIC ? tin + wave * (m * S * PPSCI_TILE) : tin;
@@ -455,7 +492,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
               constexpr int k = decltype(kc)::value;
               lacc[k * PPSCI_TILE + lane] = EPI_STATIC_FMA(lt[k], ld[k], lacc[k * PPSCI_TILE + lane]);
             });
-          if (wave == 1 && valid) {  // optional outputs, by a wave that does not carry the loss sums
+          if (!SPEC && wave == 1 && valid) {  // optional outputs, by a wave that does not carry the loss sums (SPEC: none planned)
             if (a.U != nullptr) epi_static_for<0, P::MS>([&](auto qc) { a.U[(long long)decltype(qc)::value * a.N + p] = u[decltype(qc)::value]; });
             if (args.e.Ubar != nullptr)
               epi_static_for<0, P::MS>([&](auto qc) { args.e.Ubar[(long long)decltype(qc)::value * a.N + p] = ub[decltype(qc)::value]; });
@@ -889,7 +926,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
             if (j < d_raw && !PPSCI_ABL(0)) {
               f32x4 t = hb[0] * tx[j * PPSCI_TILE + c];
 #pragma unroll
-              for (int i = 0; i < N1; ++i) t += hb[1 + i] * a.d.dirs[i][j];
+              for (int i = 0; i < N1; ++i) t += hb[1 + i] * (SPEC ? dirs_s[i * D_RAW + j] : a.d.dirs[i][j]);
               f32x4 v4;
 #pragma unroll
               for (int r = 0; r < 4; ++r) v4[r] = ppsci_row_sum16_last(t[r]);
@@ -1023,10 +1060,32 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
 }
 
 // ------------------------------------------------------------------------------------ host side
+// the shape-specialised instantiation of this unit (PPSCI_FUSED_SPEC_D_RAW / _M, set by the .hip file; STATIC units only)
+#if PPSCI_FUSED_STATIC && defined(PPSCI_FUSED_SPEC_D_RAW) && !defined(PPSCI_ABL_BUILD)
+#define PPSCI_FUSED_HAS_SPEC 1
+#define PPSCI_FUSED_SPEC_KERNEL (taylor_fused_kernel<NB, LH, N1, N2, PPSCI_ACT_ID, true, 0, PPSCI_FUSED_SPEC_D_RAW, PPSCI_FUSED_SPEC_M>)
+#else
+#define PPSCI_FUSED_HAS_SPEC 0
+#endif
+
 template <int NB, int LH, int N1, int N2>
 static int launch_fused(StepArgs& a, void* stream, int launch, int* grid_out) {
   constexpr int S = 1 + N1 + N2;
+#if PPSCI_FUSED_HAS_SPEC
+  constexpr int lds_spec = (int)(ppsci_fused_floats_spec<NB, LH, N1, N2, PPSCI_FUSED_SPEC_D_RAW, PPSCI_FUSED_SPEC_M>() * 4);
+#endif
   if (launch == 2) {
+#if PPSCI_FUSED_HAS_SPEC
+    if (a.t.spec) {  // (chosen by the plan: the shape matches and no optional output is requested)
+      PPSCI_LAUNCH(PPSCI_FUSED_SPEC_KERNEL, StepArgs, a.t.grid, 64 * NB, lds_spec, stream, a);
+      int e = PPSCI_LAST_LAUNCH_ERROR();
+      if (e != 0) {
+        ppsci_set_error("taylor_fused: launch failed (hip error %d)", e);
+        return PPSCI_E_LAUNCH;
+      }
+      return PPSCI_OK;
+    }
+#endif
 #ifdef PPSCI_ABL_BUILD
     {
       const char* ev = getenv("PPSCI_ABL");
@@ -1061,6 +1120,14 @@ static int launch_fused(StepArgs& a, void* stream, int launch, int* grid_out) {
     ppsci_set_error("taylor_fused: cannot raise dynamic LDS to %d B", lds);
     return PPSCI_E_LAUNCH;
   }
+  a.t.spec = a.t.spec_ok = 0;
+#if PPSCI_FUSED_HAS_SPEC
+  // the shape-specialised kernel runs the plan's grid in no more LDS than planned; whether the plan takes it is decided once its
+  // optional outputs are known (ppsci_taylor_step_plan)
+  if (a.f.d.d_raw == PPSCI_FUSED_SPEC_D_RAW && a.f.q.d0 == PPSCI_FUSED_SPEC_D_RAW && a.f.d.d_out == PPSCI_FUSED_SPEC_M && lds_spec <= lds &&
+      PPSCI_SET_MAX_LDS(PPSCI_FUSED_SPEC_KERNEL, lds_spec) == 0)
+    a.t.spec_ok = 1;
+#endif
   int per_cu = 1;
   if (PPSCI_OCCUPANCY((taylor_fused_kernel<NB, LH, N1, N2, PPSCI_ACT_ID, PPSCI_FUSED_STATIC != 0>), 64 * NB, lds, &per_cu) != 0 || per_cu < 1) per_cu = 1;
   const int ntl = a.f.ntiles;

@@ -5,5 +5,8 @@
 #endif
 #define PPSCI_ACT_ID PPSCI_ACT_TANH
 #define PPSCI_FUSED_STATIC 1
+// shape-specialised instantiations (taylor_fused.inc, D_RAW / M): two raw inputs, one output -- the scalar 2-D / 1-D + time PINNs
+#define PPSCI_FUSED_SPEC_D_RAW 2
+#define PPSCI_FUSED_SPEC_M 1
 #define PPSCI_FUSED_RUN_NAME ppsci_fused_static_run_tanh
 #include "taylor_fused.inc"

@@ -24,6 +24,8 @@ struct StepTail {
   int accumulate, do_adam;
   float lr_t, beta1, beta2, eps_t, grad_scale;
   int fused;           // host side only: planned onto the fused tile kernel (taylor_fused.inc)
+  int spec_ok, spec;   // host side only (fused): the shape has a shape-specialised kernel | the plan runs it (no optional outputs and
+                       // ppsci_set_fused_specialised on: ppsci_taylor_step_plan)
   int one_tail;        // host side only (with external == 1): ONE kernel behind the launch -- sums, grad (+)=, loss terms, Adam and the
                        // fragments of the updated hidden matrices (wgrad_reduce.hip wgrad_tail_kernel) -- instead of two
   int external;        // fused tile kernel: 1 = the launch stops at the workgroups' rows; the host issues the two reduction kernels

@@ -255,6 +255,11 @@ class StepPlan:
         nm = C.c_char_p()
         return (nm.value or b"").decode() if L.lib().ppsci_taylor_step_plan_static(self.handle, C.byref(nm)) > 0 else ""
 
+    @property
+    def specialised(self) -> bool:
+        """True when the plan's tile kernel is the shape-specialised instantiation (ppsci_taylor_step_plan_specialised)."""
+        return L.lib().ppsci_taylor_step_plan_specialised(self.handle) == 1
+
     def run_main(self) -> None:
         """Measurement: the main kernel of the step alone (ppsci_taylor_step_run_main)."""
         L.check(L.lib().ppsci_taylor_step_run_main(self.handle, _stream_ptr(self._dev)))

@@ -15,7 +15,7 @@ src = os.path.join("gpurun_out", f"prof_{tag}")
 os.makedirs("profiles", exist_ok=True)
 shutil.copy(os.path.join(src, "trace", "ac_kernel_stats.csv"), os.path.join("profiles", f"{out_stem}_kernel_stats.csv"))
 summary = {}
-for sub in ("pmc_fetch", "pmc_write", "pmc_mfma", "pmc_wait"):
+for sub in ("pmc_fetch", "pmc_write", "pmc_mfma", "pmc_wait", "pmc_salu"):
     path = os.path.join(src, sub, "ac_counter_collection.csv")
     if not os.path.exists(path):
         continue
