@@ -369,6 +369,12 @@ int ppsci_taylor_step_plan_static(const ppsci_step_plan* plan, const char** name
  * shape-specialised kernel, else 0. */
 void ppsci_set_fused_specialised(int on);
 int ppsci_taylor_step_plan_specialised(const ppsci_step_plan* plan);
+/* Shape-specialised kernels of depth >= 3 whose larger LDS carve-up still lets two workgroups share a CU keep the split planes the
+ * forward sweep publishes for layer L-2 in a third exchange buffer and do not evaluate, split and publish them again in the
+ * reverse sweep (csrc/taylor_fused.inc, KEEP) -- same values, same order.  0 keeps every plan on the kernel that recomputes (tests
+ * and tools compare the two); default on.  Read when a launch is PLANNED.  _plan_keep_planes: 1 when the plan runs a KEEP kernel. */
+void ppsci_set_fused_keep_planes(int on);
+int ppsci_taylor_step_plan_keep_planes(const ppsci_step_plan* plan);
 int ppsci_taylor_step(const ppsci_mlp_desc* d, const ppsci_epilogue_desc* e, float* params, int64_t n_points,
                       const float* const* inputs_host, const float* const* aux_host, float* U, float* Ubar,
                       float* residual_out, void* stash, void* workspace, int64_t workspace_bytes, float* loss_terms,

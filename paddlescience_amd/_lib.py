@@ -191,6 +191,8 @@ _SYMBOLS = {
     "ppsci_taylor_step_plan_static": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
     "ppsci_set_fused_specialised": (None, [C.c_int]),
     "ppsci_taylor_step_plan_specialised": (C.c_int, [C.c_void_p]),
+    "ppsci_set_fused_keep_planes": (None, [C.c_int]),
+    "ppsci_taylor_step_plan_keep_planes": (C.c_int, [C.c_void_p]),
     "ppsci_taylor_step_plan": (C.c_void_p, [C.POINTER(MlpDesc), C.POINTER(EpilogueDesc), C.c_void_p, C.c_int64,
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -367,8 +367,9 @@ extern "C" int ppsci_epilogue_predecode(const ppsci_epilogue_desc* e, uint32_t* 
   if (n_loads) *n_loads = nl;
   return n;
 }
-static int g_fused_spec = 1;
+static int g_fused_spec = 1, g_fused_keep = 1;
 extern "C" void ppsci_set_fused_specialised(int on) { g_fused_spec = on ? 1 : 0; }
+extern "C" void ppsci_set_fused_keep_planes(int on) { g_fused_keep = on ? 1 : 0; }
 extern "C" void ppsci_set_fused_step(int on) { g_fused_step = on ? 1 : 0; }
 extern "C" void ppsci_set_step_tail(int mode) { g_step_tail = (mode < 0 || mode > 3) ? -1 : mode; }
 // a tree over more rows than this is slower than the reduction kernels: every level is a ~10-20 us pass of ONE workgroup
@@ -606,6 +607,7 @@ extern "C" ppsci_step_plan* ppsci_taylor_step_plan(const ppsci_mlp_desc* d, cons
   a.e.resid = residual_out;
   // the shape-specialised tile kernel writes none of the optional outputs
   a.t.spec = (a.t.fused && a.t.spec_ok && g_fused_spec && !U && !Ubar && !residual_out) ? 1 : 0;
+  a.t.keep = (a.t.spec && a.t.keep_ok && g_fused_keep) ? 1 : 0;  // ... which keeps the forward sweep's split planes where it can
   a.e.partials = ws + y.rows_l;
   a.b.Ubar = Ubar;
   a.b.stash = (const f32x4*)stash;
@@ -640,6 +642,10 @@ extern "C" int ppsci_taylor_step_plan_static(const ppsci_step_plan* plan, const 
 // 1: the plan's tile kernel is the shape-specialised instantiation (taylor_fused.inc, D_RAW / M); 0: the generic one (or no fused
 // tile kernel at all)
 extern "C" int ppsci_taylor_step_plan_specialised(const ppsci_step_plan* plan) { return plan && plan->a.t.fused && plan->a.t.spec ? 1 : 0; }
+// 1: that kernel is the KEEP instantiation (the forward sweep's split planes of h_{L-3} serve the reverse sweep); 0: it recomputes them
+extern "C" int ppsci_taylor_step_plan_keep_planes(const ppsci_step_plan* plan) {
+  return plan && plan->a.t.fused && plan->a.t.spec && plan->a.t.keep ? 1 : 0;
+}
 
 extern "C" int ppsci_taylor_step_plan_set_scales(ppsci_step_plan* plan, const ppsci_epilogue_desc* e) {
   if (!plan || !e || e->n_res != plan->a.e.e.n_res) {

@@ -43,6 +43,12 @@
 #define PPSCI_FUSED_EPI_SCRATCH ((PPSCI_MAX_RES + PPSCI_MAX_EPARAM) * 16)  // epi_finale's LDS (floats)
 #define PPSCI_FUSED_SPEC_TAB (64 + PPSCI_MAX_RES + PPSCI_MAX_DIRS * PPSCI_FUSED_MAX_IN)  // shape-specialised kernels: LDS table floats
 #define PPSCI_FUSED_MAX_IN 4  // raw inputs held in registers per lane (x, y, z, t); nets with more take the separate launches
+// KEEP kernels of even depth (taylor_fused_kernel): 1 = the h_0 planes that reverse layer 1 recomputes go to the keep buffer `kx`
+// too, so that nothing of a tile's last Wbar GEMM reads `hx` and the WAR barrier in front of the next tile's first publish is
+// gone; 0 = they go to `hx` and the barrier stays (A/B builds; the kept planes of layer L-2 do not depend on this)
+#ifndef PPSCI_FUSED_KEEP_H0
+#define PPSCI_FUSED_KEEP_H0 1
+#endif
 // x[j] for a runtime j out of the register array (a select chain: dynamic indexing would put the array into scratch)
 #define PPSCI_FUSED_XJ(x, j) ((j) == 0 ? (x)[0] : ((j) == 1 ? (x)[1] : ((j) == 2 ? (x)[2] : (x)[3])))
 
@@ -107,17 +113,24 @@ static inline long long ppsci_fused_floats(const ppsci_mlp_desc& d, const ppsci_
 
 // LDS floats of one workgroup of a shape-specialised kernel (the kernel's carve-up with its compile-time shape): what a STATIC
 // plan never touches is left out -- the VM register file, `uls`, `rres` and all of the program tables but the constants and scales
-template <int NB, int LH, int N1, int N2, int D_RAW, int M>
+// KEEP: a third exchange buffer `kx` behind `hx`; to stay within half a CU, `ered` (used behind the tile loop only) aliases `zx`
+// and `dz0` holds the N1 rows that are used instead of PPSCI_MAX_DIRS
+template <int NB, int LH, int N1, int N2, int D_RAW, int M, bool KEEP = false>
 static constexpr long long ppsci_fused_floats_spec() {
   constexpr int S = 1 + N1 + N2, HP = 16 * NB, pad4m = ((M + 3) / 4) * 4;
   long long fl = 2LL * ((D_RAW + LH + M) * HP + pad4m);        // W0s Bs WLs BLs | gW0 gB gWL gBL
   fl += 2LL * NB * M * S * PPSCI_TILE;                         // tin | red
   fl += NB * D_RAW * PPSCI_TILE;                               // tinx
-  fl += PPSCI_FUSED_EPI_SCRATCH + PPSCI_MAX_RES * PPSCI_TILE;  // ered | lacc
+  fl += (KEEP ? 0 : PPSCI_FUSED_EPI_SCRATCH) + PPSCI_MAX_RES * PPSCI_TILE;  // ered | lacc
   fl += PPSCI_FUSED_SPEC_TAB;                                  // constants | scales | directions
-  fl += 2LL * S * NB * 3 * 64 * 2;                             // zx | hx
-  fl += PPSCI_MAX_DIRS * HP;                                   // dz0
+  fl += (KEEP ? 3LL : 2LL) * S * NB * 3 * 64 * 2;              // zx | hx (| kx)
+  fl += (KEEP ? N1 : PPSCI_MAX_DIRS) * HP;                     // dz0
   return fl;
+}
+// KEEP is instantiated where there is a layer to keep planes for and two workgroups of the larger carve-up share a CU
+template <int NB, int LH, int N1, int N2, int D_RAW, int M>
+static constexpr bool ppsci_fused_keep_fits() {
+  return LH >= 3 && 4 * ppsci_fused_floats_spec<NB, LH, N1, N2, D_RAW, M, true>() <= PPSCI_LDS_LIMIT_BYTES / 2;
 }
 
 // STATIC: the kernel of plans whose residual program is a compile-time table (args.e.static_id > 0, epi_static.h) AND whose
@@ -128,11 +141,21 @@ static constexpr long long ppsci_fused_floats_spec() {
 // them, every offset of the LDS carve-up (ppsci_fused_floats_spec) and the guards of the optional outputs (U, dL/dU, residual
 // values: such plans take the D_RAW = M = 0 kernel) leave the tile loop, and with them the uniform values the compiler kept
 // alive for them across the loop in spilled SGPRs.  Same arithmetic, order, barriers and exchange layouts.
-template <int NB, int LH, int N1, int N2, int ACT, bool STATIC, int ABL = 0, int D_RAW = 0, int M = 0>
+// KEEP (shape-specialised kernels with L >= 3): h_{L-3} is split once per tile instead of twice -- the
+// split planes of h_{L-3}, which forward layer L-2 publishes (paired layout) for its GEMM, are written a second time into a third
+// exchange buffer `kx` in the unpaired layout [S][NB][3][64]; reverse layer L-2 reads them there as the A operand of its Wbar
+// GEMM instead of evaluating, splitting and publishing h_{L-3} from the stash again (for l = L-1 the forward sweep's last
+// publish already serves: HPAIR).  Same values, same MFMA sequence, same barriers in the reverse sweep.  The hazard table of the
+// three buffers is in DESIGN 4.2.
+template <int NB, int LH, int N1, int N2, int ACT, bool STATIC, int ABL = 0, int D_RAW = 0, int M = 0, bool KEEP = false>
 __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args) {
   constexpr int S = 1 + N1 + N2;
   constexpr bool SPEC = D_RAW > 0;
   static_assert(!SPEC || (STATIC && M > 0 && D_RAW <= PPSCI_FUSED_MAX_IN), "shape-specialised kernels are STATIC kernels");
+  static_assert(!KEEP || (SPEC && LH >= 3 && ABL == 0), "planes are kept by shape-specialised kernels with a layer L-2 >= 1");
+  // even depth: reverse layer 1 publishes its recomputed h_0 into kx (free there: its readers, Wbar_{L-2}, are behind that layer's
+  // first barrier for every wave) -- then nothing of a tile's last Wbar GEMM reads hx, where the next tile's first publish goes
+  constexpr bool KEEP_H0 = KEEP && PPSCI_FUSED_KEEP_H0 != 0 && (LH % 2) == 0 && LH >= 4;
   constexpr int HP = 16 * NB;
   constexpr int W = NB;
   constexpr int L = LH;
@@ -160,15 +183,20 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
   float* uls = tin + W * m * S * PPSCI_TILE;       // [m*S][16] U of the tile (pre-decoded programs with a VGPR register file)
   float* tinx = uls + (SPEC ? 0 : m * S * PPSCI_TILE);  // [W][d_raw][16] inputs of the tile as the residual program / reverse layer 0 read them
   float* red = tinx + W * d_raw * PPSCI_TILE;      // [W][m*S][16] last-linear partial sums
-  float* ered = red + W * m * S * PPSCI_TILE;      // epi_finale scratch
-  float* lacc = ered + PPSCI_FUSED_EPI_SCRATCH;    // [PPSCI_MAX_RES][16] loss sums of the VM lanes
+  float* ered = red + W * m * S * PPSCI_TILE;      // epi_finale scratch (KEEP: no region of its own, see below)
+  float* lacc = ered + (KEEP ? 0 : PPSCI_FUSED_EPI_SCRATCH);  // [PPSCI_MAX_RES][16] loss sums of the VM lanes
   float* rf = lacc + PPSCI_MAX_RES * PPSCI_TILE;   // VM register file: values [n][16] | adjoints [n][16]
   unsigned* ftab = (unsigned*)(rf + 2 * n_instr * PPSCI_TILE);  // tables of the pre-decoded program (epi_fast_init)
   float* rres = (float*)(ftab + EPI_FAST_WORDS + PPSCI_MAX_RES);  // [PPSCI_MAX_RES][16] residual values of the tile
   // (SPEC: no uls / rf / rres; of the tables only the 64 constants, the PPSCI_MAX_RES scales and the N1 x D_RAW directions)
   u32x2* zx = (u32x2*)(SPEC ? (float*)ftab + PPSCI_FUSED_SPEC_TAB : rres + PPSCI_MAX_RES * PPSCI_TILE);  // [S][NB][3][64] split planes (paired layout): zbar_l; forward: h of odd layers
   u32x2* hx = zx + S * NB * 3 * 64;                     // the same: h_{l-1};                             forward: h of even layers
-  float* dz0 = (float*)(hx + S * NB * 3 * 64);  // [N1][HP]: z_0 of the first-derivative streams when every input is raw (below)
+  u32x2* kx = hx + S * NB * 3 * 64;                     // KEEP: [S][NB][3][64] split planes (unpaired): h_{L-3} of the forward sweep
+  float* dz0 = (float*)(hx + (KEEP ? 2 : 1) * S * NB * 3 * 64);  // [N1][HP]: z_0 of the first-derivative streams when every input is raw (below)
+  // KEEP: epi_finale's scratch is zx -- it runs behind the tile loop and the __syncthreads() in front of the row stores, when no
+  // wave reads an exchange buffer any more
+  if constexpr (KEEP) ered = (float*)zx;
+  static_assert(!KEEP || PPSCI_FUSED_EPI_SCRATCH * 4 <= S * NB * 3 * 64 * 8, "ered must fit into zx");
   f32x4* zsave = (f32x4*)hx;  // [L][S][64]: wave 0 parks its stash here while it runs the residual program (both exchange
                               // buffers are idle between the sweeps; L x S KiB <= the S x NB x 1.5 KiB of one for L <= 6)
   static_assert(L * S * 64 * 16 <= S * NB * 3 * 64 * 8, "zsave must fit into hx");
@@ -361,8 +389,14 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
         // Wbar GEMM: no second evaluation, split and publish of h_{L-2} there.  For even L the first
         // publish of a tile then goes to hx as well, which the previous tile's last Wbar GEMM may still be reading in another
         // wave: one barrier in front of it (behind the layer-0 arithmetic: nobody waits long).
+        // KEEP_H0: that GEMM reads kx instead, and kx is written behind this sweep's barriers only: no barrier here.
         u32x2* xb = STATIC ? (((L - 1 - l) & 1) ? zx : hx) : ((l & 1) ? zx : hx);
-        if constexpr (STATIC && l == 1 && (L % 2) == 0) ppsci_block_sync_lds();
+        if constexpr (STATIC && l == 1 && (L % 2) == 0 && !KEEP_H0) ppsci_block_sync_lds();
+        // KEEP, l == L-2: the planes go to kx as well (unpaired, as the reverse publish of this layer wrote them into hx).  L == 3:
+        // this is the tile's first publish and there is no barrier between it and the previous tile's last Wbar GEMM, which
+        // reads kx in other waves -- the copy is written BEHIND this layer's barrier (from registers), not in front of it.
+        constexpr bool KFWD = KEEP && l == L - 2, KLATE = KFWD && l == 1;
+        ppsci_split4 spk[KLATE ? S : 1];
         const u32x4* gf = (const u32x4*)a.xfrag + (long long)(l - 1) * PPSCI_GFRAG_PER_LAYER(NB) + lanel;
         u32x4 Ak[NKP][3];
 #pragma unroll
@@ -375,9 +409,20 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
 #pragma unroll
           for (int q = 0; q < 3; ++q)
             if (!PPSCI_ABL(9) || (sp.p[q][0] == 0x12345u && sp.p[q][1] == 0x54321u)) xb[ppsci_xpair(NB, s, wave, q, xcl)] = sp.p[q];
+          if constexpr (KLATE) spk[s] = sp;
+          else if constexpr (KFWD) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) kx[((s * NB + wave) * 3 + q) * 64 + xcl] = sp.p[q];
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
         ppsci_block_sync_lds();
+        if constexpr (KLATE) {
+#pragma unroll
+          for (int s = 0; s < S; ++s)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) kx[((s * NB + wave) * 3 + q) * 64 + xcl] = spk[s].p[q];
+        }
         PPSCI_FT(2)
         h[0] = *(const f32x4*)&Bs[l * HP + 16 * wave + 4 * g];
 #pragma unroll
@@ -659,6 +704,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
     // One layer of the reverse sweep (taylor_bwd_wx.inc, with the stash in registers):
     //   pointwise adjoint -> zbar_l -> split planes to zx                                          | barrier
     //   hbar_{l-1} = W_l zbar_l (B = zx) ; h_{l-1} from the stash -> split planes to hx            | barrier
+    //     (not where the forward sweep left them: l = L-1 of STATIC kernels, HPAIR; l = L-2 of KEEP kernels, in kx)
     //   Wbar_l += h_{l-1} (x) zbar_l  (A = hx, all blocks; B = the own block of zx; both through the transpose read)
     auto bwd_layer = [&](auto lc) {
       constexpr int l = decltype(lc)::value;
@@ -820,8 +866,12 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
         PPSCI_FT(8)
         // ---- h_{l-1} streams of the own block (the A operand of Wbar_l) from the stash of layer l-1 -> hx
         // (STATIC kernels, l == L-1: the forward sweep's last publish IS that operand -- in the paired layout of the B reads)
+        // (KEEP kernels, l == L-2: the forward sweep left its planes in kx, in the layout this publish writes; KEEP_H0, l == 1:
+        // published into kx instead of hx)
         constexpr bool HPAIR = STATIC && l == L - 1;
-        if (!PPSCI_ABL(3) && !HPAIR) {
+        constexpr bool HKEPT = KEEP && l == L - 2;
+        u32x2* const ha = (HKEPT || (KEEP_H0 && l == 1)) ? kx : hx;  // A operand of Wbar_l
+        if (!PPSCI_ABL(3) && !HPAIR && !HKEPT) {
           f32x4 E1, E2, E3;
           f32x4 hcs[S];
           if (PPSCI_ABL(7)) {
@@ -839,13 +889,13 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
             const ppsci_split4 sp = ppsci_fused_split<ABL>(hcs[s]);
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-              if (!PPSCI_ABL(9) || (sp.p[q][0] == 0x12345u && sp.p[q][1] == 0x54321u)) hx[((s * NB + wave) * 3 + q) * 64 + xcl] = sp.p[q];
+              if (!PPSCI_ABL(9) || (sp.p[q][0] == 0x12345u && sp.p[q][1] == 0x54321u)) ha[((s * NB + wave) * 3 + q) * 64 + xcl] = sp.p[q];
             __builtin_amdgcn_sched_barrier(0);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
-        // hx (h_{l-1}) complete.  (HPAIR: nothing was published, but the barrier stays: the next layer overwrites zx, which the
-        // other waves read -- all blocks -- in the hbar GEMM above)
+        // hx (h_{l-1}) complete.  (HPAIR, HKEPT: nothing was published, but the barrier stays: the next layer overwrites zx, which
+        // the other waves read -- all blocks -- in the hbar GEMM above)
         if (!PPSCI_ABL(3)) ppsci_block_sync_lds();
         PPSCI_FT(9)
         // ---- Wbar_l[all ib, own column block] += h_{l-1}[ib] (x) zbar_l[own]   (contraction over stream x point)
@@ -853,7 +903,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
 #pragma unroll 1
         for (int sp = 0; sp + 1 < (PPSCI_ABL(3) ? 0 : S); sp += 2) {
           int zs_ = ppsci_xpair(NB, sp, wave, 0, xtl);                                    // zx: paired layout
-          int hs_ = HPAIR ? ppsci_xpair(NB, sp, 0, 0, xtl) : xtl + sp * NB * 3 * 64;      // hx: [S][NB][3][64], or paired
+          int hs_ = HPAIR ? ppsci_xpair(NB, sp, 0, 0, xtl) : xtl + sp * NB * 3 * 64;      // hx / kx: [S][NB][3][64], or paired
           PPSCI_OPAQUE(zs_);
           PPSCI_OPAQUE(hs_);
           u32x2 zN0[3], zN1[3];
@@ -874,8 +924,8 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
                   hN0[buf][e][q] = ppsci_lds_read_tr16(&hx[hs_ + (((ig + e) >> 1) * 3 + q) * 128 + ((ig + e) & 1)]);
                   hN1[buf][e][q] = ppsci_lds_read_tr16(&hx[hs_ + ((NKP + ((ig + e) >> 1)) * 3 + q) * 128 + ((ig + e) & 1)]);
                 } else {
-                  hN0[buf][e][q] = ppsci_lds_read_tr16(&hx[hs_ + ((ig + e) * 3 + q) * 64]);
-                  hN1[buf][e][q] = ppsci_lds_read_tr16(&hx[hs_ + ((NB + ig + e) * 3 + q) * 64]);
+                  hN0[buf][e][q] = ppsci_lds_read_tr16(&ha[hs_ + ((ig + e) * 3 + q) * 64]);
+                  hN1[buf][e][q] = ppsci_lds_read_tr16(&ha[hs_ + ((NB + ig + e) * 3 + q) * 64]);
                 }
               }
           };
@@ -903,7 +953,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
           for (int e = 0; e < NB; ++e)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-              hN0[e][q] = ppsci_lds_read_tr16(HPAIR ? &hx[ppsci_xpair(NB, S - 1, e, q, xtl)] : &hx[(((S - 1) * NB + e) * 3 + q) * 64 + xtl]);
+              hN0[e][q] = ppsci_lds_read_tr16(HPAIR ? &hx[ppsci_xpair(NB, S - 1, e, q, xtl)] : &ha[(((S - 1) * NB + e) * 3 + q) * 64 + xtl]);
 #pragma unroll
           for (int q = 0; q < PPSCI_XDL_NPROD; ++q)
 #pragma unroll
@@ -996,7 +1046,7 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
 
     PPSCI_FT(11)
     // (no barrier here: tin / red are rewritten behind the next tile's own barriers, which every wave reaches only after
-    // this tile's reverse sweep; the exchange planes zx / hx likewise -- see the forward layer's comment)
+    // this tile's reverse sweep; the exchange planes zx / hx / kx likewise -- see the forward layer's comment)
     PPSCI_FT(12)
   }
 #ifdef PPSCI_FUSED_TIMERS
@@ -1067,6 +1117,14 @@ __global__ void __launch_bounds__(64 * NB, 2) taylor_fused_kernel(StepArgs args)
 #else
 #define PPSCI_FUSED_HAS_SPEC 0
 #endif
+// ... and its KEEP twin (PPSCI_FUSED_KEEP_PLANES, set by the .hip file), instantiated where ppsci_fused_keep_fits; not in the timer
+// builds, whose per-phase sums live in `ered` during the tile loop
+#if PPSCI_FUSED_HAS_SPEC && defined(PPSCI_FUSED_KEEP_PLANES) && PPSCI_FUSED_KEEP_PLANES && !defined(PPSCI_FUSED_TIMERS)
+#define PPSCI_FUSED_HAS_KEEP 1
+#define PPSCI_FUSED_KEEP_KERNEL (taylor_fused_kernel<NB, LH, N1, N2, PPSCI_ACT_ID, true, 0, PPSCI_FUSED_SPEC_D_RAW, PPSCI_FUSED_SPEC_M, true>)
+#else
+#define PPSCI_FUSED_HAS_KEEP 0
+#endif
 
 template <int NB, int LH, int N1, int N2>
 static int launch_fused(StepArgs& a, void* stream, int launch, int* grid_out) {
@@ -1077,6 +1135,12 @@ static int launch_fused(StepArgs& a, void* stream, int launch, int* grid_out) {
   if (launch == 2) {
 #if PPSCI_FUSED_HAS_SPEC
     if (a.t.spec) {  // (chosen by the plan: the shape matches and no optional output is requested)
+#if PPSCI_FUSED_HAS_KEEP
+      if constexpr (ppsci_fused_keep_fits<NB, LH, N1, N2, PPSCI_FUSED_SPEC_D_RAW, PPSCI_FUSED_SPEC_M>()) {
+        if (a.t.keep) PPSCI_LAUNCH(PPSCI_FUSED_KEEP_KERNEL, StepArgs, a.t.grid, 64 * NB, a.t.lds_keep, stream, a);
+        else PPSCI_LAUNCH(PPSCI_FUSED_SPEC_KERNEL, StepArgs, a.t.grid, 64 * NB, lds_spec, stream, a);
+      } else
+#endif
       PPSCI_LAUNCH(PPSCI_FUSED_SPEC_KERNEL, StepArgs, a.t.grid, 64 * NB, lds_spec, stream, a);
       int e = PPSCI_LAST_LAUNCH_ERROR();
       if (e != 0) {
@@ -1120,7 +1184,7 @@ static int launch_fused(StepArgs& a, void* stream, int launch, int* grid_out) {
     ppsci_set_error("taylor_fused: cannot raise dynamic LDS to %d B", lds);
     return PPSCI_E_LAUNCH;
   }
-  a.t.spec = a.t.spec_ok = 0;
+  a.t.spec = a.t.spec_ok = a.t.keep = a.t.keep_ok = a.t.lds_keep = 0;
 #if PPSCI_FUSED_HAS_SPEC
   // the shape-specialised kernel runs the plan's grid in no more LDS than planned; whether the plan takes it is decided once its
   // optional outputs are known (ppsci_taylor_step_plan)
@@ -1130,6 +1194,19 @@ static int launch_fused(StepArgs& a, void* stream, int launch, int* grid_out) {
 #endif
   int per_cu = 1;
   if (PPSCI_OCCUPANCY((taylor_fused_kernel<NB, LH, N1, N2, PPSCI_ACT_ID, PPSCI_FUSED_STATIC != 0>), 64 * NB, lds, &per_cu) != 0 || per_cu < 1) per_cu = 1;
+#if PPSCI_FUSED_HAS_KEEP
+  // The KEEP kernel needs MORE LDS than planned: it is taken only if as many of its workgroups share a CU as the grid below is
+  // computed from -- grid, iters and workspace rows are those of the plan either way.
+  if constexpr (ppsci_fused_keep_fits<NB, LH, N1, N2, PPSCI_FUSED_SPEC_D_RAW, PPSCI_FUSED_SPEC_M>()) {
+    constexpr int lds_keep = (int)(ppsci_fused_floats_spec<NB, LH, N1, N2, PPSCI_FUSED_SPEC_D_RAW, PPSCI_FUSED_SPEC_M, true>() * 4);
+    int pc = 0;
+    if (a.t.spec_ok && PPSCI_SET_MAX_LDS(PPSCI_FUSED_KEEP_KERNEL, lds_keep) == 0 &&
+        PPSCI_OCCUPANCY(PPSCI_FUSED_KEEP_KERNEL, 64 * NB, lds_keep, &pc) == 0 && pc == per_cu) {
+      a.t.keep_ok = 1;
+      a.t.lds_keep = lds_keep;
+    }
+  }
+#endif
   const int ntl = a.f.ntiles;
   int grid = ntl < PPSCI_NUM_CU * per_cu ? ntl : PPSCI_NUM_CU * per_cu;
   if (ppsci_get_max_grid() > 0 && grid > ppsci_get_max_grid()) grid = ppsci_get_max_grid();

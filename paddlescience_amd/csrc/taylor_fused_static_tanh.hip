@@ -8,5 +8,9 @@
 // shape-specialised instantiations (taylor_fused.inc, D_RAW / M): two raw inputs, one output -- the scalar 2-D / 1-D + time PINNs
 #define PPSCI_FUSED_SPEC_D_RAW 2
 #define PPSCI_FUSED_SPEC_M 1
+// ... and their KEEP twins where the carve-up fits half a CU: L = 3, 4, 5 of the stream sets with S <= 4
+#ifndef PPSCI_FUSED_KEEP_PLANES
+#define PPSCI_FUSED_KEEP_PLANES 1
+#endif
 #define PPSCI_FUSED_RUN_NAME ppsci_fused_static_run_tanh
 #include "taylor_fused.inc"

@@ -26,6 +26,9 @@ struct StepTail {
   int fused;           // host side only: planned onto the fused tile kernel (taylor_fused.inc)
   int spec_ok, spec;   // host side only (fused): the shape has a shape-specialised kernel | the plan runs it (no optional outputs and
                        // ppsci_set_fused_specialised on: ppsci_taylor_step_plan)
+  int keep_ok, keep;   // host side only (fused): the specialised kernel has a KEEP twin that runs the planned grid (taylor_fused.inc) |
+                       // the plan runs it (spec and ppsci_set_fused_keep_planes on)
+  int lds_keep;        // host side only: dynamic LDS bytes of the KEEP kernel (more than `lds`)
   int one_tail;        // host side only (with external == 1): ONE kernel behind the launch -- sums, grad (+)=, loss terms, Adam and the
                        // fragments of the updated hidden matrices (wgrad_reduce.hip wgrad_tail_kernel) -- instead of two
   int external;        // fused tile kernel: 1 = the launch stops at the workgroups' rows; the host issues the two reduction kernels

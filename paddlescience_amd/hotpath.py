@@ -260,6 +260,11 @@ class StepPlan:
         """True when the plan's tile kernel is the shape-specialised instantiation (ppsci_taylor_step_plan_specialised)."""
         return L.lib().ppsci_taylor_step_plan_specialised(self.handle) == 1
 
+    @property
+    def keep_planes(self) -> bool:
+        """True when that kernel keeps the forward sweep's split planes for the reverse sweep (ppsci_taylor_step_plan_keep_planes)."""
+        return L.lib().ppsci_taylor_step_plan_keep_planes(self.handle) == 1
+
     def run_main(self) -> None:
         """Measurement: the main kernel of the step alone (ppsci_taylor_step_run_main)."""
         L.check(L.lib().ppsci_taylor_step_run_main(self.handle, _stream_ptr(self._dev)))
