@@ -7,7 +7,15 @@ Adam.  Synthetic points `default_rng(42+rank).uniform([0,-1],[1,1])`, Xavier-uni
 gradient when N > 1) + fused Adam, inputs resident in HBM.  One process per GPU
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`); per-GPU work is fixed => weak scaling.
 
-The same JSON line also carries
+A PLAIN run (`bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]`) does what that headline figure needs and nothing
+else: set-up, the W warm-up steps, the K timed steps, the outputs of the last one if asked for, the JSON line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the windows' min / max, the final loss; also the residual-only rate, whose 31
+launches in front of the warm-up set the clock state `ms_per_step` has always been read in).  Everything below takes runs of its
+own and sits behind `--full`.
+
+With `--full` the same JSON line also carries
+  * `roofline` and `cpu_baseline` of the primary workload (launches of the main kernel alone behind the timed steps, the
+                    torch-CPU port on the same batch);
   * `parity`     -- the TIMED net (initial weights) on the first 2 048 points of the timed batch against
                     tests/golden/bench_nets.npz, i.e. values produced by running the reference's own Python in fp64
                     (tests/golden/make_bench_nets_golden.py): residual / gradient rel-L2, loss rel;
@@ -18,7 +26,8 @@ The same JSON line also carries
                     rank-strided over the N ranks (N = 1: all of them on one GPU), one SUM all-reduce of the flat
                     gradient (66 819 floats = 267 KB) per step; `value` = 1e6 / step time, "scaling": "strong".
 Rank 0 prints ONE JSON line.  The oracle (oracle/) is used by the `cpu_baseline` legs and, as the CHECKER of the
-cfg 4 / cfg 5 parity entries, never inside a timed region.
+cfg 4 / cfg 5 parity entries, never inside a timed region and never by a plain run.  `--no-cpu-baseline`, `--no-secondary` and
+`--no-strong` take single legs out of a `--full` run.
 """
 from __future__ import annotations
 
@@ -946,9 +955,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the cfg 1/3/4/5 entries (N = 1 only anyway)")
-    ap.add_argument("--no-strong", action="store_true", help="skip the 1 M-point NavierStokes strong-scaling entry")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: parity against the reference-run "
+                         "fixtures, the kernel-level roofline figures, cpu_baseline, the secondary / extra configurations, the "
+                         "strong-scaling entry (off by default: a plain run sets up, warms up, times the steps and prints)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the torch-CPU legs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the cfg 1/3/4/5 entries (N = 1 only anyway)")
+    ap.add_argument("--no-strong", action="store_true", help="with --full: skip the 1 M-point NavierStokes strong-scaling entry")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed (weights, gradient, Adam moments, loss "
                          "terms) as DIR/<name>.npy")
@@ -1003,7 +1016,8 @@ def main():
 
     flat = bench_weights(2, [WIDTH] * HIDDEN, 1)
     X = np.random.default_rng(42 + rank).uniform([0, -1], [1, 1], (N_PER_GPU, 2)).astype(np.float32)
-    parity = parity_allen_cahn(dev, flat, X) if rank == 0 and not EMU else None
+    full = args.full
+    parity = parity_allen_cahn(dev, flat, X) if full and rank == 0 and not EMU else None
     # MSE-mean over the GLOBAL batch: the all-reduce is then a pure SUM
     lay, cst = allen_cahn_constraint(dev, X, N_PER_GPU * world)
     params = torch.tensor(flat, device=dev)
@@ -1014,11 +1028,12 @@ def main():
     S = cst.streams.S
     flops_bwd = 4.0 * p_mat * S * N_PER_GPU   # reverse sweep: 2 GEMMs per layer  (F_T - F_R)
     flops_fwd = 2.0 * p_mat * S * N_PER_GPU   # F_R
-    # the 100 000-point step at the INITIAL weights (gradient + loss, no update): `parity.full_batch` compares it with the
-    # fp32 CPU port's first step on the same batch (cpu_baseline runs it anyway)
-    eng.forward_backward([cst])
-    _sync()
-    g0, loss0 = eng.grad.detach().cpu().numpy().copy(), cst.losses()["allen_cahn"]
+    if full:
+        # the 100 000-point step at the INITIAL weights (gradient + loss, no update): `parity.full_batch` compares it with the
+        # fp32 CPU port's first step on the same batch (cpu_baseline runs it anyway)
+        eng.forward_backward([cst])
+        _sync()
+        g0, loss0 = eng.grad.detach().cpu().numpy().copy(), cst.losses()["allen_cahn"]
     eng.train_step([cst], 1e-3)  # (plans the step)
     fused = cst.one_launch_ready() and getattr(cst, "_step_kind", 0) == hp.STEP_FUSED_TILE and eng.one_launch
     # Timing.  `--steps K` is the number of timed steps: K steps back to back behind the W warm-up
@@ -1043,6 +1058,11 @@ def main():
 
     last = None
     with quiet_host():
+        # SURVEY.md 8(d) "R": residual evaluation only -- forward streams + epilogue, no stash, no adjoints.  In EVERY run, plain
+        # ones included: these 31 launches (~4 ms of GPU work) directly in front of the warm-up are part of what `ms_per_step`
+        # means -- they take the GPU off its idle clocks.  Measured on MI355X, --steps 20 --warmup 5, five alternating runs
+        # each: without them the median `ms_per_step` reads 0.2480 (0.2432 - 0.2504), with them 0.2336 (0.2335 - 0.2352), as
+        # it always did (0.2328, 0.2293 - 0.2337, on the commit before `--full` existed).
         t_res = time_events(lambda: cst.forward(params, False), 30, median=True)
         for _ in range(args.warmup):
             eng.train_step([cst], 1e-3)
@@ -1059,7 +1079,7 @@ def main():
             # (copies of the last step's results before the kernel-only launches below reuse the plan's buffers)
             last = {"params": eng.params, "grad": eng.grad, "adam_m": eng.m, "adam_v": eng.v, "loss_terms": cst.loss_terms}
             last = {name: t.detach().clone() for name, t in last.items()}
-        main_samples = time_events_list(cst._step_plan.run_main, 6 * WINDOWS) if fused and not EMU else []
+        main_samples = time_events_list(cst._step_plan.run_main, 6 * WINDOWS) if full and fused and not EMU else []
     assert sum(sizes) == args.steps
     tt = torch.tensor(wins, device=dev, dtype=torch.float64)
     if world > 1:
@@ -1068,44 +1088,60 @@ def main():
     dt = wins[(len(wins) - 1) // 2]  # the median window (lower median for an even count)
     if last is not None:
         dump_outputs(args.dump_outputs, last)
-    t_main = (float(np.median(main_samples)) if main_samples else time_events(cst._step_plan.run_main, 1)) if fused else None
     loss = cst.losses()["allen_cahn"]
 
-    # (t_res: SURVEY.md 8(d) "R", residual evaluation only -- forward streams + epilogue, no stash, no adjoints; measured above)
-    if fused:
-        # the dominant kernel IS the step: forward + residual program + reverse of every tile in one kernel (F_T flops);
-        # HIP events on the launch stream around that kernel alone (no weight split, no reduction kernels)
-        kname = f"taylor_fused_kernel<4, {HIDDEN}, 2, 1, 0, {'true' if cst._step_plan.static_program else 'false'}>"
-        flops_main = flops_fwd + flops_bwd
-        ach = flops_main / t_main / 1e12
-        extra = {"kernel_ms": t_main * 1e3, "flops_per_launch": flops_main,
-                 "residual_program": ("compile-time table `%s` (csrc/epi_static_programs.h): evaluated by every wave" % cst._step_plan.static_program)
-                 if cst._step_plan.static_program else "epilogue VM on wave 0",
-                 "step_launches": "tile kernel + one tail kernel (sums, loss terms, Adam, next step's weight fragments)",
-                 "what": "forward Taylor streams + residual program + loss seeds + reverse sweep of every 16-point tile in one "
-                         "kernel: the activation stash never leaves the CU (registers), U / dL/dU live in LDS"}
-        ksub = "taylor_fused_kernel<4, 4, 2, 1"
-    else:
-        # per-kernel timing of the dominant kernel (reverse sweep) with HIP events on the launch stream;
-        # ppsci_taylor_bwd = the reverse kernel + the two small fixed-order reduction kernels behind it (~10 us)
-        kname = "taylor_bwd_wx_kernel<4, 1, 4, 2, 1, 0>"
-        t_fwd = time_events(lambda: hp.taylor_fwd(cst.desc, params, cst.inputs, cst.U, cst.stash))
-        t_bwd = time_events(lambda: cst.backward(params))
-        ach = flops_bwd / t_bwd / 1e12
-        extra = {"kernel_ms": t_bwd * 1e3, "fwd_kernel_ms": t_fwd * 1e3, "fwd_achieved": flops_fwd / t_fwd / 1e12,
-                 "flops_per_launch": flops_bwd}
-        ksub = "taylor_bwd_wx_kernel<4, 1, 4, 2, 1"
+    roofline = None
+    if full:
+        t_main = (float(np.median(main_samples)) if main_samples else time_events(cst._step_plan.run_main, 1)) if fused else None
+        if fused:
+            # the dominant kernel IS the step: forward + residual program + reverse of every tile in one kernel (F_T flops);
+            # HIP events on the launch stream around that kernel alone (no weight split, no reduction kernels)
+            kname = f"taylor_fused_kernel<4, {HIDDEN}, 2, 1, 0, {'true' if cst._step_plan.static_program else 'false'}>"
+            flops_main = flops_fwd + flops_bwd
+            ach = flops_main / t_main / 1e12
+            extra = {"kernel_ms": t_main * 1e3, "flops_per_launch": flops_main,
+                     "residual_program": ("compile-time table `%s` (csrc/epi_static_programs.h): evaluated by every wave" % cst._step_plan.static_program)
+                     if cst._step_plan.static_program else "epilogue VM on wave 0",
+                     "step_launches": "tile kernel + one tail kernel (sums, loss terms, Adam, next step's weight fragments)",
+                     "what": "forward Taylor streams + residual program + loss seeds + reverse sweep of every 16-point tile in one "
+                             "kernel: the activation stash never leaves the CU (registers), U / dL/dU live in LDS"}
+            ksub = "taylor_fused_kernel<4, 4, 2, 1"
+        else:
+            # per-kernel timing of the dominant kernel (reverse sweep) with HIP events on the launch stream;
+            # ppsci_taylor_bwd = the reverse kernel + the two small fixed-order reduction kernels behind it (~10 us)
+            kname = "taylor_bwd_wx_kernel<4, 1, 4, 2, 1, 0>"
+            t_fwd = time_events(lambda: hp.taylor_fwd(cst.desc, params, cst.inputs, cst.U, cst.stash))
+            t_bwd = time_events(lambda: cst.backward(params))
+            ach = flops_bwd / t_bwd / 1e12
+            extra = {"kernel_ms": t_bwd * 1e3, "fwd_kernel_ms": t_fwd * 1e3, "fwd_achieved": flops_fwd / t_fwd / 1e12,
+                     "flops_per_launch": flops_bwd}
+            ksub = "taylor_bwd_wx_kernel<4, 1, 4, 2, 1"
 
-    # HBM traffic of the dominant kernel per launch and of the whole step: quoted from the newest committed rocprofv3
-    # summary (tools/profile_bench.sh; separate --pmc passes, FETCH_SIZE doubled per MI355X_MICROARCH.md) with its file name
-    prof = profile_info("bench", ksub, dt * 1e3, once_per_step=True)
-    traffic, traffic_src = prof.get("kernel_hbm_bytes_per_launch"), prof.get("source")
+        # HBM traffic of the dominant kernel per launch and of the whole step: quoted from the newest committed rocprofv3
+        # summary (tools/profile_bench.sh; separate --pmc passes, FETCH_SIZE doubled, as tools/summarize_profile.py
+        # explains) with its file name
+        prof = profile_info("bench", ksub, dt * 1e3, once_per_step=True)
+        traffic, traffic_src = prof.get("kernel_hbm_bytes_per_launch"), prof.get("source")
+        roofline = {"bound": "mfma", "kernel": kname, "achieved": ach,
+                    "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP32_TFLOPS,
+                    **pipe_roofline(ach, "bench", ksub),
+                    "traffic": traffic, "traffic_source": traffic_src, **extra,
+                    "algorithmic_bytes_per_launch": 4.0 * (2 + 1 + 1) * N_PER_GPU,
+                    "arithmetic": "fp32 operands as three bf16 terms, six v_mfma_f32_16x16x32_bf16 products per "
+                                  "K = 32 step, fp32 accumulate (error <= the fp32 MFMA's); `peak` is the fp32-input "
+                                  "MFMA peak the algorithmic flops are priced against, `pipe_peak` the ceiling of the "
+                                  "pipe they actually run on",
+                    "residual_error_note": "residual rel-L2 vs the fp64 reference run is ~1.1e-6 = 2.5x the fp32 floor of "
+                                           "the reference algorithm itself (4.4e-7, SURVEY 8d): the 5-slot tanh "
+                                           "(1 - 2/(exp(2x)+1), abs error 1.2e-7), not the bf16 split",
+                    "step_profile": prof}
 
     strong = None
-    import tempfile
+    if full:
+        import tempfile
 
-    tmp = tempfile.mkdtemp(prefix="ppsci_bench_")
-    if not args.no_strong:
+        tmp = tempfile.mkdtemp(prefix="ppsci_bench_")
+    if full and not args.no_strong:
         try:
             strong = strong_ns(tmp, world, rank, 1 if EMU else max(5, args.steps // 5), 0 if EMU else max(2, args.warmup // 3),
                                barrier)
@@ -1134,20 +1170,7 @@ def main():
                                    "residual+MSE-mean+grad+Adam (BASELINE.json configs[1])",
                        "points_per_gpu": N_PER_GPU, "parallelism": f"dp{world}", "loss": loss,
                        "residual_only_points_per_s_per_gpu": N_PER_GPU / t_res},
-            "roofline": {"bound": "mfma", "kernel": kname, "achieved": ach,
-                         "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP32_TFLOPS,
-                         **pipe_roofline(ach, "bench", ksub),
-                         "traffic": traffic, "traffic_source": traffic_src, **extra,
-                         "algorithmic_bytes_per_launch": 4.0 * (2 + 1 + 1) * N_PER_GPU,
-                         "arithmetic": "fp32 operands as three bf16 terms, six v_mfma_f32_16x16x32_bf16 products per "
-                                       "K = 32 step, fp32 accumulate (error <= the fp32 MFMA's); `peak` is the fp32-input "
-                                       "MFMA peak the algorithmic flops are priced against, `pipe_peak` the ceiling of the "
-                                       "pipe they actually run on",
-                         "residual_error_note": "residual rel-L2 vs the fp64 reference run is ~1.1e-6 = 2.5x the fp32 floor of "
-                                                "the reference algorithm itself (4.4e-7, SURVEY 8d): the 5-slot tanh "
-                                                "(1 - 2/(exp(2x)+1), abs error 1.2e-7), not the bf16 split",
-                         "step_profile": prof},
-            "parity": parity,
+            **({"roofline": roofline, "parity": parity} if full else {}),
         }
         if strong is not None:
             out["strong_scaling"] = strong
@@ -1164,7 +1187,7 @@ def main():
         # gradient on the launch stream, ONE launch for Adam + the next step's weight fragments (engine.Engine.train_step)
         out["config"]["dp_step"] = ("fused tile kernel + tail kernel (sums) -> all-reduce (%d B) -> Adam + fragments kernel"
                                     % (int(eng.grad.numel()) * 4)) if world > 1 else "fused tile kernel + tail kernel (sums, Adam, fragments)"
-        if world == 1 and not args.no_cpu_baseline and not EMU:
+        if full and world == 1 and not args.no_cpu_baseline and not EMU:
             out["cpu_baseline"] = cpu_baseline("allen_cahn", flat, X)
             out["speedup_vs_cpu_best_thread"] = out["value"] / out["cpu_baseline"]["value"]
             l_cpu, g_cpu = out["cpu_baseline"].pop("_first_step")
@@ -1174,7 +1197,7 @@ def main():
                 "loss_rel": abs(loss0 / l_cpu - 1.0), "grad_rel_l2": rel(g0, g_cpu),
                 "note": "both sides are fp32 sums over 100 000 points in different orders: the comparison carries the port's "
                         "own rounding (the fp64-anchored figures are the 2 048-point ones above)"}
-        if world == 1 and not args.no_secondary and not EMU:
+        if full and world == 1 and not args.no_secondary and not EMU:
             k, w = max(10, args.steps // 2), max(3, args.warmup // 2)
             sec = []
             for fn in (lambda: secondary_laplace(tmp, 4 * k, w, not args.no_cpu_baseline),

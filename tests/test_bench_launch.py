@@ -1,5 +1,6 @@
 """bench.py's launch contract on the CPU SIMT emulator (gloo, tiny sizes; PPSCI_BENCH_EMU=1 is a test-only mode):
-`python bench.py --gpus 2` WITHOUT a launcher must start two ranks itself and print one JSON line that says so."""
+`python bench.py --gpus 2` WITHOUT a launcher must start two ranks itself and print one JSON line that says so.  A plain run
+carries the headline figures only; the strong-scaling entry (like every other extra leg) is asked for with `--full`."""
 import json
 import os
 import subprocess
@@ -24,7 +25,7 @@ def test_bench_gpus2_self_launches_two_ranks():
     from tests.emu import build_emu
 
     build_emu.build()  # once, before two ranks race for the build directory
-    r = _run({}, ["--gpus", "2", "--steps", "1", "--warmup", "1"])
+    r = _run({}, ["--full", "--gpus", "2", "--steps", "1", "--warmup", "1"])
     assert r["n_gpus"] == 2 and r["config"]["parallelism"] == "dp2" and r["steps"] == 1
     assert "EMULATOR TEST MODE" in r["data"]
     s = r["strong_scaling"]
@@ -39,7 +40,7 @@ def test_bench_gpus8_as_the_driver_launches_it():
     from tests.emu import build_emu
 
     build_emu.build()
-    r = _run({}, ["--gpus", "8", "--steps", "1", "--warmup", "0"])
+    r = _run({}, ["--full", "--gpus", "8", "--steps", "1", "--warmup", "0"])
     assert r["n_gpus"] == 8 and r["config"]["parallelism"] == "dp8" and r["scaling"] == "weak"
     s = r["strong_scaling"]
     assert s["n_gpus"] == 8 and s["comm_world_size"] == 8 and s["comm_backend"] == "gloo" and s["scaling"] == "strong"
@@ -54,6 +55,23 @@ def test_bench_gpus8_as_the_driver_launches_it():
     assert c["comm_world_size"] == 8 and c["comm_backend"] == "gloo"
     # the primary step under data parallelism: the fused tile kernel stays, Adam + fragments in one launch behind the all-reduce
     assert "all-reduce" in c["dp_step"] and "Adam + fragments" in c["dp_step"]
+
+
+def test_bench_plain_run_carries_the_headline_only(tmp_path):
+    """Without `--full`: set-up, warm-up, the timed steps, the dumped outputs, the line -- none of the legs that take runs of
+    their own (parity, roofline, cpu_baseline, secondary, strong scaling)."""
+    from tests.emu import build_emu
+
+    build_emu.build()
+    r = _run({}, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")])
+    assert r["metric"] == "collocation-points/sec (PDE residual+grad)" and r["unit"] == "points/s" and r["dtype"] == "f32"
+    assert r["higher_is_better"] is True and r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 1
+    assert r["value"] > 0 and r["ms_per_step_min"] <= r["ms_per_step"] <= r["ms_per_step_max"]
+    assert abs(r["value"] * r["ms_per_step"] * 1e-3 / r["config"]["points_per_gpu"] - 1.0) < 1e-9
+    for k in ("parity", "roofline", "cpu_baseline", "secondary", "strong_scaling"):
+        assert k not in r, k
+    assert "strong_points_per_s" not in r["config"] and r["config"]["loss"] > 0
+    assert sorted(os.listdir(tmp_path / "dump")) == ["adam_m.npy", "adam_v.npy", "grad.npy", "loss_terms.npy", "params.npy"]
 
 
 def test_bench_refuses_a_launcher_world_that_differs_from_gpus():

@@ -7,7 +7,7 @@ mkdir -p $O
 if [ $# -gt 0 ]; then T="$*"; else T="tests"; fi
 timeout 2400 python -m pytest $T -m gpu -q -x > $O/tests.log 2>&1
 tail -4 $O/tests.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || tail -c 600 $O/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || tail -c 600 $O/bench.err
 python - <<'PY'
 import json
 r = json.load(open("gpurun_out/check/bench.json"))

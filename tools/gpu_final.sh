@@ -8,7 +8,7 @@ O=gpurun_out/final
 mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q > $O/tests.log 2>&1
 grep -E "passed|failed" $O/tests.log | tail -2
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 r = json.load(open("gpurun_out/final/bench.json"))

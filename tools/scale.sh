@@ -16,7 +16,7 @@ mkdir -p $O
 timeout 900 python bench.py --steps $STEPS --warmup $WARMUP --no-secondary --no-cpu-baseline > $O/plain.json 2> $O/plain.err || { echo "plain bench.py failed"; tail -5 $O/plain.err; exit 1; }
 for N in 1 2 4 8; do
   if [ "$N" -gt "$NGPU" ]; then echo "N=$N: only $NGPU GPU(s) here -- skipped"; continue; fi
-  timeout 1800 python bench.py --gpus $N --steps $STEPS --warmup $WARMUP --no-secondary --no-cpu-baseline > $O/n$N.json 2> $O/n$N.err \
+  timeout 1800 python bench.py --full --gpus $N --steps $STEPS --warmup $WARMUP --no-secondary --no-cpu-baseline > $O/n$N.json 2> $O/n$N.err \
     || { echo "bench.py --gpus $N failed"; tail -5 $O/n$N.err; exit 1; }
 done
 python - "$O" <<'PY'
