@@ -536,8 +536,10 @@ int ppsci_dft2_kept_fwd_from(int n, int H, int W, int modes_x, int modes_y, int 
 int ppsci_dft2_kept_inv_from(int n, int H, int W, int modes_x, int modes_y, int Hs, int Ws, const float* Z, float* y, void* stream);
 int ppsci_dft2_kept_fwd(int n, int H, int W, int modes_x, int modes_y, int rows, const float* x, float* X, void* stream);
 int ppsci_dft2_kept_inv(int n, int H, int W, int modes_x, int modes_y, int rows, const float* Z, float* y, void* stream);
-/* ppsci_dft2_kept_inv that also leaves the first pass of the block tail behind: rows_out[plane][4] gets the sums of
- * y + sbias[plane % C] and of its square (ppsci_fno_tail_fwd_ex with have_rows = 1 then skips its statistics pass). */
+/* ppsci_dft2_kept_inv that also leaves the first pass of the block tail behind: rows_out[plane][4] gets the row statistics of
+ * u = y + sbias[plane % C] -- [0] the fp32 row mean mr, [1] sum (u - mr)^2, [2] sum (u - mr), from sums every thread keeps relative to
+ * the first element it produced; never sum u^2, which loses (mean / std)^2 ulps -- and ppsci_fno_tail_fwd_ex with have_rows = 1 then
+ * skips its statistics pass. */
 int ppsci_dft2_kept_inv_stats(int n, int H, int W, int modes_x, int modes_y, int rows, const float* Z, float* y,
                               const float* sbias, int C, float* rows_out, void* stream);
 /* ppsci_spectral_conv2d_fwd_kept + ppsci_dft2_kept_inv (rows_out NULL) / ppsci_dft2_kept_inv_stats (rows_out: [B * c_out][4], sbias:
@@ -660,7 +662,7 @@ int ppsci_fno_tail_bwd(int B, int C, int P, int norm, int gelu, const float* v, 
                        float* gv, float* ggamma, float* gbeta, float* gsbias, void* stream);
 /* The block tail next to the kept-mode transforms: a workgroup of the apply kernels produces one whole [H, W] plane, so it
  * can transform that plane from LDS instead of storing it for a transform launch to read back.
- *   _fwd_ex: have_rows != 0 -- `rows` already holds the row sums (ppsci_dft2_kept_inv_stats): no statistics pass;
+ *   _fwd_ex: have_rows != 0 -- `rows` already holds the row statistics (ppsci_dft2_kept_inv_stats): no statistics pass;
  *            X_next != NULL -- also emits the kept modes (input rows) of y = the next block's input, [B*C, mx, my, 2].
  *   _bwd_ex: ghat != NULL -- also emits the kept modes (OUTPUT rows) of gv = dL/dv, which only the spectral branch's
  *            backward reads; gv may then be NULL (never stored);

@@ -31,6 +31,11 @@ class UNOBlock(torch.nn.Module):
 
     def __init__(self, in_channels: int, out_channels: int, n_modes, scaling, norm: Optional[str], fno_skip: str, fft_norm: str):
         super().__init__()
+        if fno_skip == "identity" and in_channels != out_channels:
+            # the identity skip is added to the block's output plane by plane: with unequal channel counts the tail kernels
+            # would index [B, out_channels] planes in a [B, in_channels] tensor (the reference fails on the addition's shapes)
+            raise ValueError(f"fno_skip='identity' needs in_channels == out_channels in every block, got {in_channels} (after the "
+                             f"U-skip concatenation) and {out_channels}")
         self.in_channels, self.out_channels = in_channels, out_channels
         self.scaling = tuple(float(s) for s in scaling)
         self.n_layers, self.stabilizer = 1, None

@@ -14,11 +14,26 @@ struct DftArgs {
   float* dst;
   const float* tab;  // twiddles tw [W][my][2] | th [H][mx][2], computed once per shape on the host in double (a "plan")
   int n, H, W, mx, my, c0, rows;
-  // inverse only: also the row sums of the GroupNorm that follows (sum of y + sbias[c], sum of its square -> rows_out[p][4])
+  // inverse only: also the row statistics of the GroupNorm that follows (of y + sbias[c] -> rows_out[p][4], dft_inv_row_stats)
   const float* sbias;
   float* rows_out;
   int C;
 };
+
+// sum over the 256 threads of the workgroup, fixed order (inside a wave by shuffles, the four waves through `red`: 4 floats of
+// LDS); result in every thread
+__device__ __forceinline__ float ppsci_block_sum256(float v, float* red) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  v += __shfl_xor(v, 8, 64);
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
 
 // LDS (floats): tw [W][my][2] | th [H][mx][2] | plane [H*W] (fwd) or Z [mx*my*2] (inv) | T [H][my][2] | fwd: partial sums
 __device__ __forceinline__ void dft_twiddles(const DftArgs& a, float* tw) {
@@ -151,5 +166,38 @@ __device__ __forceinline__ void dft_inv_stages(const DftArgs& a, const float* tw
         if (hh < a.H) emit(hh, w, acc[rr]);
       }
     }
+  }
+}
+
+// GroupNorm row statistics of the plane u = y + sb a workgroup produces with dft_inv_stages, for the block tail (fno.hip
+// gn_apply_kernel), without a second look at the plane.  Every thread keeps its elements relative to the first one it saw:
+//   DftRowAcc::add(u):  K = the first u;  s1 = sum (u - K),  s2 = sum (u - K)^2,  n = their count
+// dft_inv_row_stats turns these into  stat[0] = mr, the row mean as far as fp32 sums give it;  stat[1] = sum (u - mr)^2 and
+// stat[2] = sum (u - mr), each thread's share rebased from K to mr:  sum (u - mr) = n (K - mr) + s1,
+// sum (u - mr)^2 = s2 + (K - mr) (2 s1 + n (K - mr)).  The row's exact mean is mr + stat[2] / P and its squared deviations
+// about that mean are stat[1] - stat[2]^2 / P.  Every term is of the size of the deviations: there is no sum(u^2) - P mean^2,
+// which loses (mean / std)^2 ulps on a field with an offset.  red: 4 floats of LDS; fixed order, so bit-reproducible.
+struct DftRowAcc {
+  float K = 0.f, s1 = 0.f, s2 = 0.f;
+  int n = 0;
+  __device__ __forceinline__ void add(float u) {
+    if (n == 0) K = u;
+    const float e = u - K;
+    s1 += e;
+    s2 += e * e;
+    ++n;
+  }
+};
+
+__device__ __forceinline__ void dft_inv_row_stats(const DftArgs& a, const DftRowAcc& t, float* red, float* stat) {
+  const float n = (float)t.n;
+  const float mr = ppsci_block_sum256(n * t.K + t.s1, red) / (float)(a.H * a.W);
+  const float dk = t.K - mr;
+  const float d1 = ppsci_block_sum256(n * dk + t.s1, red);
+  const float d2 = ppsci_block_sum256(t.s2 + dk * (2.f * t.s1 + n * dk), red);
+  if (threadIdx.x == 0) {
+    stat[0] = mr;
+    stat[1] = d2;
+    stat[2] = d1;
   }
 }

@@ -858,7 +858,7 @@ struct GnArgs {
   const float* skip;   // [B, C, P] or null
   float* t;            // [B, C, P] pre-activation
   float* y;            // [B, C, P] or null (== t when there is no activation)
-  float* rows;         // [B*C][4]: per-row sums (forward: sum u, sum u^2; backward: sum gt, sum gt*xh, sum xh)
+  float* rows;         // [B*C][4] per row: forward the fp32 mean mr, sum (u - mr)^2, sum (u - mr); backward sum gt, sum gt*xh, sum xh
   float* stats;        // [B][2]: mean, rstd
   const float* gout;   // backward: dL/dy
   const float* gout2;  // backward: a second addend of dL/dy, or null (the spectral branch's share of the next block)
@@ -878,20 +878,6 @@ __device__ __forceinline__ void gn_to_plane(float* pl, int W, int p, int P, f32x
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (p + k < P) pl[p + k + (p + k) / W] = v[k];
-}
-
-__device__ __forceinline__ float fno_block_sum(float v, float* red) {
-  // sum over the 256 threads of the workgroup, fixed order; result in every thread
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // sums of two doubles over the 256 threads, fixed-shape tree in LDS (red: 512 doubles); results in every thread
@@ -918,7 +904,7 @@ __global__ void __launch_bounds__(256) gn_rowstats_kernel(GnArgs a) {
   const int row = blockIdx.x, c = row % a.C;
   const float* vr = a.v + (long long)row * a.P;
   const float sb = a.sbias ? a.sbias[c] : 0.f;
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f;
   constexpr bool al = AL;
   for (int p = threadIdx.x * 4; p < a.P; p += 1024) {
     f32x4 u = fno_ld4(vr, p, a.P, al) + sb;
@@ -928,13 +914,28 @@ __global__ void __launch_bounds__(256) gn_rowstats_kernel(GnArgs a) {
         if (p + k >= a.P) u[k] = 0.f;
     }
     s1 += (u[0] + u[1]) + (u[2] + u[3]);
-    s2 += (u[0] * u[0] + u[1] * u[1]) + (u[2] * u[2] + u[3] * u[3]);
   }
-  s1 = fno_block_sum(s1, red);
-  s2 = fno_block_sum(s2, red);
+  // The variance comes from squared deviations, never from sum(u^2) - P mean^2 (which loses (mean / std)^2 ulps: a field
+  // with an offset).  mr: the row mean as far as fp32 sums give it; a second sweep over the row (hot in cache) takes the
+  // deviations about it.  The row's exact mean is mr + d1 / P, its squared deviations about that are d2 - d1^2 / P.
+  const float mr = ppsci_block_sum256(s1, red) / (float)a.P;
+  float d1 = 0.f, d2 = 0.f;
+  for (int p = threadIdx.x * 4; p < a.P; p += 1024) {
+    f32x4 dd = (fno_ld4(vr, p, a.P, al) + sb) - mr;
+    if (!al) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k >= a.P) dd[k] = 0.f;
+    }
+    d1 += (dd[0] + dd[1]) + (dd[2] + dd[3]);
+    d2 += (dd[0] * dd[0] + dd[1] * dd[1]) + (dd[2] * dd[2] + dd[3] * dd[3]);
+  }
+  d1 = ppsci_block_sum256(d1, red);
+  d2 = ppsci_block_sum256(d2, red);
   if (threadIdx.x == 0) {
-    a.rows[(long long)row * 4 + 0] = s1;
-    a.rows[(long long)row * 4 + 1] = s2;
+    a.rows[(long long)row * 4 + 0] = mr;
+    a.rows[(long long)row * 4 + 1] = d2;
+    a.rows[(long long)row * 4 + 2] = d1;
   }
 }
 
@@ -954,14 +955,22 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(GnArgs a) {
   const long long base = (long long)row * a.P;
   float mean = 0.f, rstd = 1.f;
   if (a.norm) {
-    double s1 = 0.0, s2 = 0.0;
+    // the C rows of the sample merged in double: row c has the mean m_c = mr + d1 / P and the squared deviations
+    // M2_c = d2 - d1^2 / P about it (gn_rowstats_kernel; dft_inv_row_stats in dft_kept.h), and
+    //   var = (sum_c M2_c + P sum_c (m_c - m)^2) / n,  the row means taken relative to row 0's (K)
+    const double Pd = (double)a.P;
+    const float* r0 = a.rows + (long long)b * a.C * 4;
+    const double K = (double)r0[0] + (double)r0[2] / Pd;
+    double s = 0.0, q = 0.0;
     for (int cc = threadIdx.x; cc < a.C; cc += 256) {
-      s1 += (double)a.rows[((long long)b * a.C + cc) * 4 + 0];
-      s2 += (double)a.rows[((long long)b * a.C + cc) * 4 + 1];
+      const double mr = (double)r0[cc * 4 + 0], d2 = (double)r0[cc * 4 + 1], d1 = (double)r0[cc * 4 + 2];
+      const double dm = (mr + d1 / Pd) - K;
+      s += dm;
+      q += (d2 - d1 * d1 / Pd) + Pd * dm * dm;
     }
-    fno_block_sum_d2(s1, s2, red);
-    const double n = (double)a.C * a.P, m = s1 / n;
-    double var = s2 / n - m * m;
+    fno_block_sum_d2(s, q, red);
+    const double n = (double)a.C * Pd, m = K + s / (double)a.C;
+    double var = (q - Pd * s * s / (double)a.C) / n;
     if (var < 0.0) var = 0.0;
     mean = (float)m;
     rstd = (float)(1.0 / sqrt(var + (double)a.eps));
@@ -1048,9 +1057,9 @@ __global__ void __launch_bounds__(256) gn_bwd_rows_kernel(GnArgs a) {
     r2 += (g4[0] * xh[0] + g4[1] * xh[1]) + (g4[2] * xh[2] + g4[3] * xh[3]);
     r3 += (xh[0] + xh[1]) + (xh[2] + xh[3]);
   }
-  r1 = fno_block_sum(r1, red);
-  r2 = fno_block_sum(r2, red);
-  r3 = fno_block_sum(r3, red);
+  r1 = ppsci_block_sum256(r1, red);
+  r2 = ppsci_block_sum256(r2, red);
+  r3 = ppsci_block_sum256(r3, red);
   if (threadIdx.x == 0) {
     a.rows[(long long)row * 4 + 0] = r1;
     a.rows[(long long)row * 4 + 1] = r2;
@@ -1199,7 +1208,7 @@ extern "C" int ppsci_fno_tail_fwd(int B, int C, int P, int norm, int gelu, float
   return fno_tail_fwd_run(B, C, P, norm, gelu, eps, v, sbias, gamma, beta, skip, rows, stats, t, y, 0, 0, 0, 0, 0, nullptr, stream);
 }
 
-// ppsci_fno_tail_fwd with: have_rows != 0 -- `rows` already holds the row sums of v + sbias (ppsci_dft2_kept_inv_stats wrote
+// ppsci_fno_tail_fwd with: have_rows != 0 -- `rows` already holds the row statistics of v + sbias (ppsci_dft2_kept_inv_stats wrote
 // them): no statistics pass;  X_next != NULL -- the apply kernel also emits the kept modes (input rows) of y, the next
 // block's input ([B*C, modes_x, modes_y, 2]; H * W == P, ppsci_dft2_kept_supported): no transform launch reads y back.
 extern "C" int ppsci_fno_tail_fwd_ex(int B, int C, int P, int norm, int gelu, float eps, const float* v, const float* sbias,

@@ -434,7 +434,7 @@ __global__ void __launch_bounds__(256) dft2_kept_inv_kernel(DftArgs a) {
   float* th = tw + 2 * a.W * a.my;
   float* Z = th + 2 * a.H * a.mx;
   float* T = Z + 2 * a.mx * a.my;
-  float* sred = T + 2 * a.H * a.my;  // 512 floats: the row sums' tree
+  float* sred = T + 2 * a.H * a.my;  // 512 floats reserved; the row statistics' sums use four (dft_inv_row_stats)
   const int tid = threadIdx.x, P = a.H * a.W, nm = a.mx * a.my;
   bool first = true;
   for (int p = blockIdx.x; p < a.n; p += gridDim.x) {
@@ -457,30 +457,13 @@ __global__ void __launch_bounds__(256) dft2_kept_inv_kernel(DftArgs a) {
     __syncthreads();
     float* y = a.dst + (long long)p * P;
     const float sb = (a.rows_out && a.sbias) ? a.sbias[p % a.C] : 0.f;
-    float s1 = 0.f, s2 = 0.f;
+    DftRowAcc acc;
     dft_inv_stages(a, tw, th, Z, T, [&](int hh, int w, float val) {
       y[(long long)hh * a.W + w] = val;
-      const float u = val + sb;
-      s1 += u;
-      s2 += u * u;
+      acc.add(val + sb);
     });
-    if (a.rows_out) {  // the block tail's first pass (gn_rowstats_kernel) for free: the plane is in this workgroup's registers
-      __syncthreads();
-      sred[tid] = s1;
-      sred[256 + tid] = s2;
-      __syncthreads();
-      for (int wd = 128; wd > 0; wd >>= 1) {
-        if (tid < wd) {
-          sred[tid] += sred[tid + wd];
-          sred[256 + tid] += sred[256 + tid + wd];
-        }
-        __syncthreads();
-      }
-      if (tid == 0) {
-        a.rows_out[(long long)p * 4 + 0] = sred[0];
-        a.rows_out[(long long)p * 4 + 1] = sred[256];
-      }
-    }
+    // the block tail's first pass (gn_rowstats_kernel) without its launch: this workgroup has just produced the plane
+    if (a.rows_out) dft_inv_row_stats(a, acc, sred, a.rows_out + (long long)p * 4);
   }
 }
 
@@ -510,7 +493,7 @@ __global__ void __launch_bounds__(256) spectral_inv_kernel(SpecInvArgs q) {
   float* th = tw + 2 * a.W * a.my;
   float* Z = th + 2 * a.H * a.mx;
   float* T = Z + 2 * a.mx * a.my;
-  float* sred = T + 2 * a.H * a.my;            // 512 floats: the row sums' tree
+  float* sred = T + 2 * a.H * a.my;            // 512 floats reserved; the row statistics' sums use four
   float* Zp = sred + 512;                      // [SPECINV_SPLIT][mx my][2]: the parts of the channel sum
   const int tid = threadIdx.x, P = a.H * a.W, nm = a.mx * a.my;
   bool first = true;
@@ -544,32 +527,14 @@ __global__ void __launch_bounds__(256) spectral_inv_kernel(SpecInvArgs q) {
     __syncthreads();
     float* y = a.dst + (long long)p * P;
     const float sb = (a.rows_out && a.sbias) ? a.sbias[p % a.C] : 0.f;
-    float s1 = 0.f, s2 = 0.f;
+    DftRowAcc acc;
     dft_inv_stages(a, tw, th, Z, T, [&](int hh, int w, float val) {
       float* yp = &y[(long long)hh * a.W + w];
       if (q.accumulate) val += *yp;
       *yp = val;
-      const float u = val + sb;
-      s1 += u;
-      s2 += u * u;
+      acc.add(val + sb);
     });
-    if (a.rows_out) {
-      __syncthreads();
-      sred[tid] = s1;
-      sred[256 + tid] = s2;
-      __syncthreads();
-      for (int wd = 128; wd > 0; wd >>= 1) {
-        if (tid < wd) {
-          sred[tid] += sred[tid + wd];
-          sred[256 + tid] += sred[256 + tid + wd];
-        }
-        __syncthreads();
-      }
-      if (tid == 0) {
-        a.rows_out[(long long)p * 4 + 0] = sred[0];
-        a.rows_out[(long long)p * 4 + 1] = sred[256];
-      }
-    }
+    if (a.rows_out) dft_inv_row_stats(a, acc, sred, a.rows_out + (long long)p * 4);
   }
 }
 
@@ -704,8 +669,9 @@ extern "C" int ppsci_dft2_kept_inv_from(int n, int H, int W, int modes_x, int mo
   return dft_run(n, H, W, modes_x, modes_y, 1, Z, y, 1, stream, nullptr, 1, nullptr, Hs, Ws);
 }
 
-// ppsci_dft2_kept_inv + the first pass of the block tail that consumes y: rows_out[plane][4] gets sum(y + sbias[plane % C])
-// and the sum of its square (what gn_rowstats_kernel computes from a second read of y); ppsci_fno_tail_fwd_ex(have_rows = 1)
+// ppsci_dft2_kept_inv + the first pass of the block tail that consumes y: rows_out[plane][4] gets the row statistics of
+// u = y + sbias[plane % C] in gn_rowstats_kernel's form (fp32 row mean, squared deviations about it, their sum -- see
+// dft_inv_row_stats in dft_kept.h); ppsci_fno_tail_fwd_ex(have_rows = 1)
 extern "C" int ppsci_dft2_kept_inv_stats(int n, int H, int W, int modes_x, int modes_y, int rows, const float* Z, float* y,
                                          const float* sbias, int C, float* rows_out, void* stream) {
   if (!rows_out || C < 1) {

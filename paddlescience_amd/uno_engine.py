@@ -300,6 +300,7 @@ class UnoNative(FnoNative):
         else:
             _pw_conv(B, self.c_proj, co, Pout, gz2, proj[0].weight, gx, transpose=True)
         cur, other = 1, 2
+        ghs_written = set()  # sources whose U-skip gradient (ghs) this pass has written
         for i in range(nl - 1, -1, -1):
             blk, e = m.fno_blocks[i], self.blk[i]
             (H, W), (H2, W2), ci, co = e["hw"], e["hw2"], e["ci"], e["co"]
@@ -364,10 +365,16 @@ class UnoNative(FnoNative):
                 gprev = V(self.g[cur], B, cp, P)
                 gprev.copy_(gxin[:, :cp])
                 gskip = gxin[:, cp:]
+                # several layers may read one source (unonet.py:265-283 reuses skip_outputs[src]): the first consumer of this
+                # pass (the highest layer) writes the source's gradient, every later one adds to it
+                more = e["src"] in ghs_written
+                ghs_written.add(e["src"])
                 if e["rs_h"] is not None:
                     gsk = V(self.g[3], B, cs, P)
                     gsk.copy_(gskip)
-                    e["rs_h"].adjoint(B * cs, gsk, se["ghs"])
+                    e["rs_h"].adjoint(B * cs, gsk, se["ghs"], accumulate=more)
+                elif more:
+                    se["ghs"].add_(gskip)
                 else:
                     se["ghs"].copy_(gskip)
                 gx = gprev

@@ -74,7 +74,8 @@ def shapes_of(c, in_channels=3, out_channels=1):
         sh[f"fno_blocks.{i}.convs.0.weight_real"] = (prev, co, mx, my)
         sh[f"fno_blocks.{i}.convs.0.weight_imag"] = (prev, co, mx, my)
         sh[f"fno_blocks.{i}.convs.0.bias"] = (co, 1, 1)
-        sh[f"fno_blocks.{i}.fno_skips.0.weight"] = (co, prev, 1, 1)
+        if c.get("fno_skip", "linear") == "linear":  # (identity: the skip branch has no parameters)
+            sh[f"fno_blocks.{i}.fno_skips.0.weight"] = (co, prev, 1, 1)
         if c["norm"]:
             sh[f"fno_blocks.{i}.norm.0.weight"] = (co,)
             sh[f"fno_blocks.{i}.norm.0.bias"] = (co,)
@@ -98,7 +99,8 @@ def leaves_of(model, c, skips):
         out[f"fno_blocks.{i}.convs.0.weight_real"] = blk.convs.weight[0].real
         out[f"fno_blocks.{i}.convs.0.weight_imag"] = blk.convs.weight[0].imag
         out[f"fno_blocks.{i}.convs.0.bias"] = blk.convs.bias
-        out[f"fno_blocks.{i}.fno_skips.0.weight"] = blk.fno_skips[0].weight
+        if c.get("fno_skip", "linear") == "linear":
+            out[f"fno_blocks.{i}.fno_skips.0.weight"] = blk.fno_skips[0].weight
         if c["norm"]:
             out[f"fno_blocks.{i}.norm.0.weight"], out[f"fno_blocks.{i}.norm.0.bias"] = blk.norm[0].weight, blk.norm[0].bias
         if i in skips.values():
@@ -115,7 +117,7 @@ def main():
         model = unonet.UNONet(("x",), ("y",), 3, 1, c["hidden"], lifting_channels=c["lift"], projection_channels=c["proj"],
                               n_layers=n, uno_out_channels=c["outs"], uno_n_modes=c["modes"], uno_scalings=c["scal"],
                               horizontal_skips_map=c["skips"], norm=c["norm"], domain_padding=c["pad"],
-                              domain_padding_mode=c["pad_mode"], fft_norm=c["fft_norm"])
+                              domain_padding_mode=c["pad_mode"], fft_norm=c["fft_norm"], fno_skip=c.get("fno_skip", "linear"))
         shapes, skips = shapes_of(c)
         leaves = leaves_of(model, c, skips)
         assert set(leaves) == set(shapes), set(leaves) ^ set(shapes)

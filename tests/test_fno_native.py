@@ -4,7 +4,8 @@ tail, spectral contraction, all with hand-written backward; FFTs by hipFFT) agai
   * tests/golden/fno.npz -- produced by the REFERENCE's own fno_block.py / tfnonet.py (tests/golden/make_fno_golden.py):
     output rel-L2 <= 2e-5, every parameter gradient rel-L2 <= 2e-4, loss rel <= 1e-5;
   * the torch-autograd path of the same model (the previous implementation) on a larger shape;
-  * kernel-level known answers for the 1x1 convolution (forward, data gradient, weight gradient) and the block tail."""
+  * kernel-level known answers for the 1x1 convolution (forward, data gradient, weight gradient); the block tail's kernels have
+    theirs in tests/test_fno_tail.py."""
 import os
 
 import numpy as np
@@ -155,7 +156,10 @@ def test_pw_conv_and_tail_kernels_known_answers(dev, shape, npx):
     """(B, Ci, Co, P): small ragged channels (scalar weight staging), 256 x 256 (two output-channel slabs, 16-byte staging,
     2 x 2 weight-gradient tiles), channel counts that are not multiples of 16 on the vector path, one output channel, more
     output channels than one slab with a ragged tail; plane sizes that are odd (75, 301: two weight-gradient chunks) or a
-    multiple of 4 but not of 16 (100)."""
+    multiple of 4 but not of 16 (100).
+    (Despite its name this test launches the 1x1 convolution kernels only: ppsci_pw_conv and ppsci_pw_conv_wgrad.  The block
+    tail -- ppsci_fno_tail_fwd / _bwd and their _ex forms -- is pinned in tests/test_fno_tail.py; the name stays so that the
+    test's history stays in one line.)"""
     import ctypes as C
 
     from paddlescience_amd import _lib as L

@@ -27,7 +27,7 @@ def _model(c):
     model = ppsci.arch.UNONet(("x",), ("y",), 3, 1, k["hidden"], lifting_channels=k["lift"], projection_channels=k["proj"],
                               n_layers=len(k["outs"]), uno_out_channels=k["outs"], uno_n_modes=k["modes"], uno_scalings=k["scal"],
                               horizontal_skips_map=k["skips"], norm=k["norm"], domain_padding=k["pad"],
-                              domain_padding_mode=k["pad_mode"], fft_norm=k["fft_norm"])
+                              domain_padding_mode=k["pad_mode"], fft_norm=k["fft_norm"], fno_skip=k.get("fno_skip", "linear"))
     P = {n[len(c) + 7:]: G[n].astype(np.float32) for n in G.files if n.startswith(f"{c}/param/")}
     assert set(P) == {n for n, _ in torch.nn.Module.named_parameters(model)}
     model.set_state_dict(P)
@@ -79,6 +79,54 @@ def test_native_path_reproduces_reference_uno(c, dev, full_fft, monkeypatch):
     eng.forward(x)
     eng.backward(gy)
     assert torch.equal(g1, model.flat_grad)  # fixed-order sums: bit-identical
+
+
+def test_one_source_feeding_two_layers_across_another_source_layer(dev):
+    """horizontal_skips_map {3: 0, 1: 0}: layer 0's skip output feeds layer 3 (resampled 8 x 8 -> 16 x 16) and layer 1 (as it is),
+    with layer 2 between the two consumers -- the source's gradient is the sum of both shares.  Output and every parameter gradient
+    against oracle/ref_torch.uno_forward in fp64 (pinned to the reference by the uno_shared_src / uno_identity fixtures), at the
+    fixtures' tolerances."""
+    import ppsci
+    from oracle import ref_torch as R
+
+    torch.manual_seed(11)
+    outs, modes, scal = [4, 6, 4, 4], [[8, 8], [4, 4], [4, 4], [8, 8]], [[0.5, 0.5], [1, 1], [2, 2], [1, 1]]
+    skips = {3: 0, 1: 0}
+    model = ppsci.arch.UNONet(("x",), ("y",), 3, 1, 6, lifting_channels=8, projection_channels=8, n_layers=4, uno_out_channels=outs,
+                              uno_n_modes=modes, uno_scalings=scal, horizontal_skips_map=skips, norm="group_norm")
+    d = model.flat_params.device
+    rng = np.random.default_rng(7)
+    x = torch.as_tensor(rng.standard_normal((2, 3, 16, 16)).astype(np.float32)).to(d)
+    tgt = torch.as_tensor(rng.standard_normal((2, 1, 16, 16)).astype(np.float32)).to(d)
+    P = {n: p.detach().cpu().double().requires_grad_(True) for n, p in torch.nn.Module.named_parameters(model)}
+    yo = R.uno_forward(x.cpu().double(), P, outs, modes, scal, skips, "group_norm")
+    lo = ((yo - tgt.cpu().double()) ** 2).mean()
+    names = sorted(P)
+    go = dict(zip(names, torch.autograd.grad(lo, [P[n] for n in names])))
+    eng = model.native()
+    y = eng.forward(x)
+    assert rel(y.cpu().numpy(), yo.detach().numpy()) < 2e-5
+    yl = y.detach().clone().requires_grad_(True)
+    (gy,) = torch.autograd.grad(((yl - tgt) ** 2).mean(), yl)
+    model.flat_grad.fill_(float("nan"))
+    eng.backward(gy)
+    assert torch.isfinite(model.flat_grad).all()
+    for n, p in torch.nn.Module.named_parameters(model):
+        assert rel(p.grad.cpu().numpy(), go[n].numpy()) < 2e-4, n
+
+
+def test_identity_skip_with_unequal_channels_is_refused_at_construction():
+    """fno_skip="identity" adds the block's input to its output plane by plane: a block whose input channels (after the U-skip
+    concatenation) differ from its output channels cannot take it.  Construction raises; nothing is launched."""
+    import ppsci
+
+    kw = dict(lifting_channels=8, projection_channels=8, n_layers=3, uno_n_modes=[[8, 8], [4, 4], [4, 4]],
+              uno_scalings=[[0.5, 0.5], [1, 1], [2, 2]], fno_skip="identity")
+    with pytest.raises(ValueError, match="identity"):  # 6 -> 4 in the first block
+        ppsci.arch.UNONet(("x",), ("y",), 3, 1, 6, uno_out_channels=[4, 6, 6], horizontal_skips_map={}, **kw)
+    with pytest.raises(ValueError, match="identity"):  # equal widths, but the U skip widens the last block's input to 12
+        ppsci.arch.UNONet(("x",), ("y",), 3, 1, 6, uno_out_channels=[6, 6, 6], horizontal_skips_map={2: 0}, **kw)
+    ppsci.arch.UNONet(("x",), ("y",), 3, 1, 6, uno_out_channels=[6, 6, 6], horizontal_skips_map={}, **kw)  # the valid form
 
 
 @pytest.mark.parametrize("shape", [(16, 16, 8, 8), (10, 10, 20, 20), (20, 20, 19, 19), (12, 20, 18, 10), (7, 5, 7, 9)])
