@@ -557,6 +557,12 @@ int ppsci_spectral_conv2d_inv_kept(const ppsci_spectral_desc* d, int H, int W, i
 int ppsci_spectral_conv2d_inv_kept_ex(const ppsci_spectral_desc* d, int H, int W, int Hs, int Ws, int conj_t, int rows,
                                       const float* x_k, const float* w_re, const float* w_im, float scale, float* y,
                                       const float* sbias, float* rows_out, void* stream);
+/* 1 when ppsci_spectral_conv2d_inv_kept[_ex] takes this launch: the shape test of the transform it contains -- (Hs, Ws) = (0, 0):
+ * ppsci_dft2_kept_supported(H, W, ...); (Hs, Ws) > 0: modes within the Hs x Ws spectrum and ppsci_dft2_kept_from_supported(H, W, ...)
+ * -- AND room in LDS for the parts of the channel sum next to the inverse stages, which neither of those two counts (they answer
+ * for the block-tail kernels and the stand-alone transforms).  Unlike the other _supported entry points it takes both grids.  An
+ * executor asks this before it plans a block on the kept modes; 0 -> ppsci_fft2d_* with the full-spectrum entry points. */
+int ppsci_spectral_conv2d_inv_kept_supported(int H, int W, int Hs, int Ws, int modes_x, int modes_y);
 int ppsci_spectral_conv2d_fwd_kept(const ppsci_spectral_desc* d, const float* x_k, const float* w_re, const float* w_im,
                                    float* out_k, float scale, void* stream);
 int ppsci_spectral_conv2d_bwd_kept(const ppsci_spectral_desc* d, const float* x_k, const float* w_re, const float* w_im,
@@ -691,9 +697,6 @@ int ppsci_fno_tail_bwd_ex(int B, int C, int P, int norm, int gelu, const float* 
 int ppsci_sht_supported(int H, int W, int L, int M);
 int ppsci_sht_analysis(int n, int H, int W, int L, int M, const float* tw, const float* leg, const float* x, float* X, void* stream);
 int ppsci_sht_synthesis(int n, int H, int W, int L, int M, const float* tw, const float* leg, const float* Z, float* y, void* stream);
-/* ppsci_sht_contract (conj_t as there) + ppsci_sht_synthesis in one launch; y [B * (conj_t ? Ci : Co) planes of H x W]; bit-identical to the two. */
-int ppsci_sht_synthesis_contract(int B, int Ci, int Co, int conj_t, int H, int W, int L, int M, const float* tw, const float* leg,
-                                 const float* x, const float* w_re, const float* w_im, float* y, void* stream);
 int ppsci_sht_contract(int B, int Ci, int Co, int L, int M, const float* x, const float* w_re, const float* w_im, int conj_t,
                        float* out, void* stream);
 int ppsci_sht_contract_wgrad(int B, int Ci, int Co, int L, int M, const float* x, const float* g, float* gw_re, float* gw_im,

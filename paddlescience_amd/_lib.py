@@ -223,6 +223,7 @@ _SYMBOLS = {
     "ppsci_spectral_conv2d_fwd_kept": (C.c_int, [C.POINTER(SpectralDesc)] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p]),
     "ppsci_spectral_conv2d_inv_kept_ex": (C.c_int, [C.POINTER(SpectralDesc)] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppsci_spectral_conv2d_inv_kept_supported": (C.c_int, [C.c_int] * 6),
     "ppsci_spectral_conv2d_inv_kept": (C.c_int, [C.POINTER(SpectralDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppsci_spectral_conv2d_bwd_kept": (C.c_int, [C.POINTER(SpectralDesc)] + [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_float,
@@ -250,7 +251,6 @@ _SYMBOLS = {
     "ppsci_sht_supported": (C.c_int, [C.c_int] * 4),
     "ppsci_sht_analysis": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5),
     "ppsci_sht_synthesis": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5),
-    "ppsci_sht_synthesis_contract": (C.c_int, [C.c_int] * 8 + [C.c_void_p] * 7),
     "ppsci_sht_contract": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]),
     "ppsci_sht_contract_wgrad": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5),
     "ppsci_spectrum_resize": (C.c_int, [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p]),

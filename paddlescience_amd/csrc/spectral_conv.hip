@@ -704,13 +704,25 @@ extern "C" int ppsci_spectral_conv2d_bwd_kept(const ppsci_spectral_desc* d, cons
 // ppsci_spectral_conv2d_fwd_kept + ppsci_dft2_kept_inv[_stats] in one launch (spectral_inv_kernel): y [B * c_out planes of H x W].
 // _ex: (Hs, Ws) > 0 -- the inverse between two grids (ppsci_dft2_kept_inv_from); conj_t -- the data gradient: x_k = the kept modes of
 // dL/dy [B, c_out], y [B * c_in planes] = inverse transform of x_k . conj(w)^T (ppsci_spectral_conv2d_bwd_kept's gx_k + ppsci_dft2_kept_inv).
+static long long spectral_inv_lds_bytes(int H, int W, int mx, int my) {
+  return dft_lds_bytes(H, W, mx, my, 1) + 4LL * SPECINV_SPLIT * 2 * mx * my;  // the inverse stages + Zp, the parts of the channel sum
+}
+
+// 1 when the launch below takes this shape: the transform's own test (one grid, or (Hs, Ws) > 0: between two) and the LDS of
+// spectral_inv_kernel (+ the 4 KB of static LDS it holds), which is MORE than the inverse transform alone needs
+extern "C" int ppsci_spectral_conv2d_inv_kept_supported(int H, int W, int Hs, int Ws, int modes_x, int modes_y) {
+  if (Hs < 0 || (Hs > 0) != (Ws > 0)) return 0;
+  if (!(Hs > 0 ? (modes_x <= Hs && modes_y <= Ws / 2 + 1 && ppsci_dft2_kept_from_supported(H, W, modes_x, modes_y))
+               : ppsci_dft2_kept_supported(H, W, modes_x, modes_y)))
+    return 0;
+  return spectral_inv_lds_bytes(H, W, modes_x, modes_y) + 4096 <= 64 * 1024 ? 1 : 0;
+}
+
 extern "C" int ppsci_spectral_conv2d_inv_kept_ex(const ppsci_spectral_desc* d, int H, int W, int Hs, int Ws, int conj_t, int rows,
                                                  const float* x_k, const float* w_re, const float* w_im, float scale, float* y,
                                                  const float* sbias, float* rows_out, void* stream) {
-  if (!d || !x_k || !w_re || !w_im || !y || (rows != 0 && rows != 1) || d->batch < 1 || d->c_in < 1 || d->c_out < 1 ||
-      (Hs > 0) != (Ws > 0) || Hs < 0 ||
-      !(Hs > 0 ? (rows == 1 && d->modes_x <= Hs && d->modes_y <= Ws / 2 + 1 && ppsci_dft2_kept_from_supported(H, W, d->modes_x, d->modes_y))
-               : ppsci_dft2_kept_supported(H, W, d->modes_x, d->modes_y))) {
+  if (!d || !x_k || !w_re || !w_im || !y || (rows != 0 && rows != 1) || (Hs > 0 && rows != 1) || d->batch < 1 || d->c_in < 1 ||
+      d->c_out < 1 || !ppsci_spectral_conv2d_inv_kept_supported(H, W, Hs, Ws, d->modes_x, d->modes_y)) {
     ppsci_set_error("spectral_conv2d_inv_kept: invalid argument or unsupported shape");
     return PPSCI_E_INVALID;
   }
@@ -723,11 +735,7 @@ extern "C" int ppsci_spectral_conv2d_inv_kept_ex(const ppsci_spectral_desc* d, i
   SpecInvArgs q;
   q.d = DftArgs{nullptr, y, tab, n, H, W, mx, my, (H - mx) / 2, rows, sbias, rows_out, (conj_t & 1) ? d->c_in : d->c_out};
   q.x = x_k; q.wr = w_re; q.wi = w_im; q.Ci = d->c_in; q.Co = d->c_out; q.scale = scale; q.conj_t = (conj_t & 1) ? 1 : 0; q.accumulate = (conj_t & 2) ? 1 : 0;
-  const long long lds = dft_lds_bytes(H, W, mx, my, 1) + 4LL * SPECINV_SPLIT * 2 * mx * my;
-  if (lds + 4096 > 64 * 1024) {
-    ppsci_set_error("spectral_conv2d_inv_kept: %lld B of LDS", lds);
-    return PPSCI_E_UNSUPPORTED;
-  }
+  const long long lds = spectral_inv_lds_bytes(H, W, mx, my);
   const int grid = n < 8 * PPSCI_NUM_CU ? n : 8 * PPSCI_NUM_CU;
   if (PPSCI_SET_MAX_LDS(spectral_inv_kernel, (int)lds) != 0) {
     ppsci_set_error("spectral_conv2d_inv_kept: cannot raise dynamic LDS to %lld B", lds);

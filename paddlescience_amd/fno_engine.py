@@ -64,35 +64,6 @@ class FnoNative(NativeExecutor):
     """Buffer sets per input shape (batch, H, W), `backward`, the deferred weight-gradient sums: native_executor.NativeExecutor."""
 
     label, supports = "FNO", staticmethod(supports)
-    EXECUTOR_ATTRS = NativeExecutor.EXECUTOR_ATTRS + ("use_side", "_side")
-
-    def __init__(self, model):
-        super().__init__(model)
-        # A TFNO step is ~57 kernels of 5-17 us, most of them a dependent chain -- but not all: a block's skip convolution does
-        # not depend on its spectral branch (forward), and no weight gradient is needed before the end of the backward pass.
-        # PPSCI_FNO_SIDE_STREAM=1 puts those launches onto a second HIP stream, forked from and joined back into the launch stream
-        # (inside the engine's captured graph: parallel branches).  Measured on MI355X (round 5, batch 16, 64 x 64): 0.766 ms
-        # per step against 0.677 ms in one stream -- the ~15 extra fork / join edges of the replayed graph cost more than the
-        # overlapped 5-12 us kernels give back -- so it is OFF by default (kept as a tested knob).
-        self.use_side = os.environ.get("PPSCI_FNO_SIDE_STREAM", "0") == "1" and model.flat_params.is_cuda
-        self._side = None
-
-    # ------------------------------------------------------------------ second stream
-    def _fork(self):
-        """Context manager: launches inside go to the side stream, ordered behind everything issued so far on the launch stream."""
-        import contextlib
-
-        if not self.use_side:
-            return contextlib.nullcontext()
-        if self._side is None:
-            self._side = torch.cuda.Stream()
-        self._side.wait_stream(torch.cuda.current_stream())
-        return torch.cuda.stream(self._side)
-
-    def _join(self) -> None:
-        """The launch stream waits for the side stream's work."""
-        if self.use_side and self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int, H: int, W: int) -> None:
@@ -142,17 +113,18 @@ class FnoNative(NativeExecutor):
             # (each table in the storage order of the kernel that reads it: forward AND as the other transform's adjoint)
             (self.sht_a_an, self.sht_a_sy), (self.sht_b_an, self.sht_b_sy) = (
                 tuple(torch.tensor(t, **f) for t in sht_tables.kernel_layouts(T)) for T in (ta, tb))
-        # the transforms on the kept modes only (two small DFTs per plane in LDS, spectra of mx x my numbers) when a plane
-        # fits LDS; hipFFT on the full spectrum otherwise.  PPSCI_FNO_FULL_FFT=1 forces the library path (tests, timing)
-        self.kept = (not self.sht and bool(L.lib().ppsci_dft2_kept_supported(H, W, mx, my))
+        # the transforms on the kept modes only (two small DFTs per plane in LDS, spectra of mx x my numbers) when a plane fits
+        # LDS in every kernel of that path: the predicate of the largest one, the contraction inside the inverse transform, which
+        # holds ppsci_dft2_kept_supported (the stand-alone transforms, the block tails) as one of its terms; hipFFT on the full
+        # spectrum otherwise.  PPSCI_FNO_FULL_FFT=1 forces the library path (tests, timing)
+        self.kept = (not self.sht and bool(L.lib().ppsci_spectral_conv2d_inv_kept_supported(H, W, 0, 0, mx, my))
                      and os.environ.get("PPSCI_FNO_FULL_FFT", "0") != "1")
         # (the tanh stabilizer puts a pointwise function between a block's output and the next transform's input)
         self.fuse_dft = self.kept and m.fno_blocks.stabilizer != "tanh"
-        # the forward contraction inside the inverse transform's launch (PPSCI_FNO_FUSE_CONTRACT=0: two launches; A/B, tests)
-        self.fuse_contract = self.kept and os.environ.get("PPSCI_FNO_FUSE_CONTRACT", "1") != "0"
         sp = (B, Ch, mx, my, 2) if (self.kept or self.sht) else (B, Ch, H, Wf, 2)
         self.xft = [torch.empty(sp, **f) for _ in range(nl)]      # unscaled rfftn(x_l): kept for dL/dw
-        self.out_ft = torch.empty(sp, **f)  # (full spectrum: cleared + kept modes written every time, C2R destroys it)
+        if not self.kept:  # (on the kept modes the contraction's result never leaves the inverse transform's workgroup)
+            self.out_ft = torch.empty(sp, **f)  # (full spectrum: cleared + kept modes written every time, C2R destroys it)
         self.gx_ft = torch.empty(sp, **f)
         self.ghat = torch.empty(sp, **f)
         self.gsp = torch.empty((B, Ch, P), **f)
@@ -165,16 +137,10 @@ class FnoNative(NativeExecutor):
         cmax = max(Ch, self.c_lift, self.c_proj)
         self.ga = torch.empty((B, cmax, P), **f)
         self.gb = torch.empty((B, cmax, P), **f)
-        if self.use_side or os.environ.get("PPSCI_FNO_OWN_BUFFERS", "0") == "1":  # (the second knob: A/B of the working set alone)
-            # one per block: the weight gradients that read them run on the side stream, next to the following blocks' tails
-            self.gts = [torch.empty((B, Ch, P), **f) for _ in range(nl)]
-            self.gz2 = torch.empty((B, self.c_proj, P0), **f)
-        else:
-            # one stream: every reader of a block's gradient has been enqueued before the next block overwrites it -- ONE buffer
-            # for all blocks, and the projection's hidden gradient in `ga` (the working set stays where round 4 had it)
-            gt = torch.empty((B, Ch, P), **f)
-            self.gts = [gt] * nl
-            self.gz2 = self.ga.view(-1)[:B * self.c_proj * P0].view(B, self.c_proj, P0)
+        # one stream: every reader of a block's gradient has been enqueued before the next block overwrites it -- ONE buffer
+        # for all blocks, and the projection's hidden gradient in `ga` (the working set stays where round 4 had it)
+        self.gt = torch.empty((B, Ch, P), **f)
+        self.gz2 = self.ga.view(-1)[:B * self.c_proj * P0].view(B, self.c_proj, P0)
         self.gv = torch.empty((B, Ch, P), **f)
         self._wbufs: List[torch.Tensor] = []  # per-chunk partials of the weight gradients, one buffer per _wgrad call of a pass
         self._wcall = 0
@@ -188,6 +154,36 @@ class FnoNative(NativeExecutor):
         (Hp, Wp), (H0, W0) = self.hw, self.hw0
         L.check(L.lib().ppsci_pad2d(B * Ch, H0, W0, Hp, Wp, self.oh, self.ow, 1 if unpad else 0, _p(src), _p(dst),
                                     _stream_ptr(dst)))
+
+    # ------------------------------------------------------------------ the spectral layer on full spectra (hipFFT)
+    def _fft_spectral(self, d, conv, scale, hw, hw2, x, xft, out_ft, out_ft2, v) -> None:
+        """v [B, c_out] on the hw2 grid = irfftn(scale * rfftn(x [B, c_in] on the hw grid) . w, s=hw2); xft keeps the unscaled
+        rfftn(x) for the weight gradient.  hw2 != hw (a UNO block that changes resolution): the product is cropped / zero-padded
+        into out_ft2 (ppsci_spectrum_resize) in front of the inverse transform."""
+        (H, W), (H2, W2) = hw, hw2
+        st = _stream_ptr(v)
+        L.check(L.lib().ppsci_fft2d_r2c(d.batch * d.c_in, H, W, _p(x), _p(xft), st))
+        L.check(L.lib().ppsci_spectral_conv2d_fwd_scaled(C.byref(d), _p(xft), _p(conv.weight_real), _p(conv.weight_imag), _p(out_ft),
+                                                         scale, 1, st))
+        if hw2 != hw:
+            L.check(L.lib().ppsci_spectrum_resize(d.batch * d.c_out, H, W // 2 + 1, H2, W2 // 2 + 1, 0, 0, _p(out_ft), _p(out_ft2), st))
+            out_ft = out_ft2
+        L.check(L.lib().ppsci_fft2d_c2r(d.batch * d.c_out, H2, W2, _p(out_ft), _p(v), st))
+
+    def _fft_spectral_bwd(self, d, conv, scale, hw, hw2, gv, xft, ghat, ghat_in, gx_ft, gsp) -> None:
+        """The adjoint: gsp [B, c_in] on the hw grid = the spectral branch's share of dL/dx from gv = dL/dv [B, c_out] on the hw2
+        grid, and the weight gradients.  hw2 != hw: rfftn(gv) goes back through the resize (with the Hermitian weights' ratio,
+        csrc/uno.hip) into ghat_in."""
+        (H, W), (H2, W2) = hw, hw2
+        st = _stream_ptr(gsp)
+        L.check(L.lib().ppsci_fft2d_r2c(d.batch * d.c_out, H2, W2, _p(gv), _p(ghat), st))
+        if hw2 != hw:
+            L.check(L.lib().ppsci_spectrum_resize(d.batch * d.c_out, H2, W2 // 2 + 1, H, W // 2 + 1, W2, W, _p(ghat), _p(ghat_in), st))
+            ghat = ghat_in
+        L.check(L.lib().ppsci_spectral_conv2d_bwd_real_scaled(
+            C.byref(d), _p(xft), _p(conv.weight_real), _p(conv.weight_imag), _p(ghat), _p(gx_ft), _p(conv.weight_real.grad),
+            _p(conv.weight_imag.grad), scale, W, scale, 1, st))
+        L.check(L.lib().ppsci_fft2d_c2r(d.batch * d.c_in, H, W, _p(gx_ft), _p(gsp), st))
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -217,8 +213,7 @@ class FnoNative(NativeExecutor):
             conv = fb.convs[l]
             skip = fb.fno_skips[l]
             if isinstance(skip, fno_arch.Conv1x1):
-                with self._fork():  # next to the spectral branch; the tail below joins
-                    _pw_conv(B, Ch, Ch, P, xl, skip.weight, self.s)
+                _pw_conv(B, Ch, Ch, P, xl, skip.weight, self.s)
                 sk = self.s
             else:
                 sk = xl
@@ -234,21 +229,11 @@ class FnoNative(NativeExecutor):
                 mx, my = self.desc.modes_x, self.desc.modes_y
                 if not (self.fuse_dft and l > 0):
                     L.check(L.lib().ppsci_dft2_kept_fwd(B * Ch, H, W, mx, my, 0, _p(xl), _p(xft), st))
-                if self.fuse_contract:
-                    # contraction + inverse transform (+ the tail's row sums) in one launch: a workgroup contracts the kept modes
-                    # of the plane it then transforms (csrc/spectral_conv.hip spectral_inv_kernel)
-                    L.check(L.lib().ppsci_spectral_conv2d_inv_kept(
-                        C.byref(self.desc), H, W, 1, _p(xft), _p(conv.weight_real), _p(conv.weight_imag), self.inv_n, _p(v),
-                        _p(conv.bias) if nrm is not None else None, _p(self.rows) if nrm is not None else None, st))
-                else:
-                    L.check(L.lib().ppsci_spectral_conv2d_fwd_kept(C.byref(self.desc), _p(xft), _p(conv.weight_real),
-                                                                   _p(conv.weight_imag), _p(self.out_ft), self.inv_n, st))
-                    if nrm is not None:
-                        L.check(L.lib().ppsci_dft2_kept_inv_stats(B * Ch, H, W, mx, my, 1, _p(self.out_ft), _p(v), _p(conv.bias),
-                                                                  Ch, _p(self.rows), st))
-                    else:
-                        L.check(L.lib().ppsci_dft2_kept_inv(B * Ch, H, W, mx, my, 1, _p(self.out_ft), _p(v), st))
-                self._join()
+                # contraction + inverse transform (+ the tail's row sums) in one launch: a workgroup contracts the kept modes
+                # of the plane it then transforms (csrc/spectral_conv.hip spectral_inv_kernel)
+                L.check(L.lib().ppsci_spectral_conv2d_inv_kept(
+                    C.byref(self.desc), H, W, 1, _p(xft), _p(conv.weight_real), _p(conv.weight_imag), self.inv_n, _p(v),
+                    _p(conv.bias) if nrm is not None else None, _p(self.rows) if nrm is not None else None, st))
                 L.check(L.lib().ppsci_fno_tail_fwd_ex(
                     B, Ch, P, 1 if nrm is not None else 0, 0 if last else 1, float(nrm.eps) if nrm is not None else 0.0, _p(v),
                     _p(conv.bias), _p(nrm.weight) if nrm is not None else None, _p(nrm.bias) if nrm is not None else None,
@@ -259,22 +244,12 @@ class FnoNative(NativeExecutor):
             elif self.sht:  # sfnonet.py:333-354: sht -> weights per degree -> isht
                 mx, my = self.desc.modes_x, self.desc.modes_y
                 L.check(L.lib().ppsci_sht_analysis(B * Ch, H, W, mx, my, _p(self.sht_tw), _p(self.sht_a_an), _p(xl), _p(xft), st))
-                # PPSCI_SHT_FUSE_CONTRACT=1: the contraction inside the synthesis launch (bit-identical).  Measured on MI355X at the
-                # reference's shape: the synthesis grows 13.7 -> 23.6 us (128 plane-workgroups, each walking the 32 channels itself) for
-                # a 6.0 us launch saved -- 0.542 against 0.513 ms per step -- so it is OFF by default (kept as a tested knob)
-                if os.environ.get("PPSCI_SHT_FUSE_CONTRACT", "0") == "1":
-                    L.check(L.lib().ppsci_sht_synthesis_contract(B, Ch, Ch, 0, H, W, mx, my, _p(self.sht_tw), _p(self.sht_b_sy), _p(xft),
-                                                                 _p(conv.weight_real), _p(conv.weight_imag), _p(v), st))
-                else:
-                    L.check(L.lib().ppsci_sht_contract(B, Ch, Ch, mx, my, _p(xft), _p(conv.weight_real), _p(conv.weight_imag), 0,
-                                                       _p(self.out_ft), st))
-                    L.check(L.lib().ppsci_sht_synthesis(B * Ch, H, W, mx, my, _p(self.sht_tw), _p(self.sht_b_sy), _p(self.out_ft), _p(v), st))
+                # (the contraction stays a launch of its own: inside the synthesis it measured slower, HISTORY.md "removed paths")
+                L.check(L.lib().ppsci_sht_contract(B, Ch, Ch, mx, my, _p(xft), _p(conv.weight_real), _p(conv.weight_imag), 0,
+                                                   _p(self.out_ft), st))
+                L.check(L.lib().ppsci_sht_synthesis(B * Ch, H, W, mx, my, _p(self.sht_tw), _p(self.sht_b_sy), _p(self.out_ft), _p(v), st))
             else:
-                L.check(L.lib().ppsci_fft2d_r2c(B * Ch, H, W, _p(xl), _p(xft), st))
-                L.check(L.lib().ppsci_spectral_conv2d_fwd_scaled(C.byref(self.desc), _p(xft), _p(conv.weight_real),
-                                                                 _p(conv.weight_imag), _p(self.out_ft), self.inv_n, 1, st))
-                L.check(L.lib().ppsci_fft2d_c2r(B * Ch, H, W, _p(self.out_ft), _p(v), st))
-            self._join()
+                self._fft_spectral(self.desc, conv, self.inv_n, self.hw, self.hw, xl, xft, self.out_ft, None, v)
             L.check(L.lib().ppsci_fno_tail_fwd(
                 B, Ch, P, 1 if nrm is not None else 0, 0 if last else 1, float(nrm.eps) if nrm is not None else 0.0, _p(v),
                 _p(conv.bias), _p(nrm.weight) if nrm is not None else None, _p(nrm.bias) if nrm is not None else None,
@@ -300,12 +275,7 @@ class FnoNative(NativeExecutor):
         return self._wbufs[i]
 
     def _wgrad(self, B, ci, co, P, x, gy, w_param, b_param, xv=None) -> None:
-        """Weight (+ bias) gradient of a 1x1 convolution: on the side stream -- its operands are complete on the launch stream
-        at this point and are not rewritten before backward() joins (per-block `gts`, an own `gz2`) -- next to the chain."""
-        with self._fork():
-            self._wgrad_(B, ci, co, P, x, gy, w_param, b_param, xv)
-
-    def _wgrad_(self, B, ci, co, P, x, gy, w_param, b_param, xv=None) -> None:
+        """Weight (+ bias) gradient of a 1x1 convolution, as per-chunk partial rows; their sums are the pass's last launch."""
         chunks = int(L.lib().ppsci_pw_conv_wgrad_chunks(B, P))  # (P differs between the padded blocks and lifting / projection)
         wg = w_param.grad.view(-1)
         if b_param is not None and grads_adjacent(w_param, b_param):
@@ -324,14 +294,16 @@ class FnoNative(NativeExecutor):
         if b_param is not None:
             self._wsegs.append((part_b.data_ptr(), b_param.grad.view(-1).data_ptr(), chunks, co))
 
+    def _lift0_fusable(self, Ch) -> bool:
+        """ppsci_fno_lift0_wgrad's envelope for the first lifting layer's gradient (its weight and bias gradients neighbours)."""
+        w0, b0 = self.m.lifting.fcs[0].weight, self.m.lifting.fcs[0].bias
+        return (self.lift_virtual and self.m.in_channels <= 4 and Ch <= 64 and Ch % 4 == 0 and b0 is not None
+                and grads_adjacent(w0, b0))
+
     def _lift_fused_both(self, Ch) -> bool:
-        m = self.m
-        lift = m.lifting.fcs
-        w0, b0, w1, b1 = lift[0].weight, lift[0].bias, lift[1].weight, lift[1].bias
-        K0, C1 = m.in_channels, self.c_lift
-        return (self.lift_virtual and os.environ.get("PPSCI_FNO_LIFT0_FUSED", "1") != "0" and K0 <= 4 and Ch <= 32 and Ch % 4 == 0
-                and b0 is not None and b1 is not None and os.environ.get("PPSCI_FNO_LIFT1_FUSED", "1") != "0"
-                and grads_adjacent(w0, b0) and grads_adjacent(w1, b1))
+        """... and the second layer's gradient from the same pass (GELU(z1) is at hand there), its two gradients neighbours too."""
+        w1, b1 = self.m.lifting.fcs[1].weight, self.m.lifting.fcs[1].bias
+        return self._lift0_fusable(Ch) and Ch <= 32 and b1 is not None and grads_adjacent(w1, b1)
 
     def _lift_takes_addend(self, Ch) -> bool:
         """The lifting kernel is the ONLY consumer of dL/dx_0 (both lifting gradients from it, no padding in between)."""
@@ -341,32 +313,26 @@ class FnoNative(NativeExecutor):
         """Lifting MLP backward with the hidden tensor virtual: the second layer's weight gradient as before, the first layer's by
         ppsci_fno_lift0_wgrad -- GELU'(W0 x + b0) * (W1^T gx) is formed in registers and reduced against the input channels at
         once (was: 67 MB written by one launch and read back by the next at batch 16, 64 x 64).  False: shape outside the kernel's
-        envelope or PPSCI_FNO_LIFT0_FUSED=0 -- the caller takes the two-launch path."""
-        m = self.m
-        K0, C1 = m.in_channels, self.c_lift
-        w0, b0 = lift[0].weight, lift[0].bias
-        if (os.environ.get("PPSCI_FNO_LIFT0_FUSED", "1") == "0" or K0 > 4 or Ch > 64 or Ch % 4 != 0 or b0 is None
-                or not grads_adjacent(w0, b0)):
+        envelope -- the caller takes the two-launch path."""
+        if not self._lift0_fusable(Ch):
             return False
-        w1, b1 = lift[1].weight, lift[1].bias
-        # the second layer's gradient from the same pass (GELU(z1) is at hand there) when its weight and bias gradients are neighbours
-        both = (Ch <= 32 and b1 is not None and grads_adjacent(w1, b1)
-                and os.environ.get("PPSCI_FNO_LIFT1_FUSED", "1") != "0")
+        K0, C1 = self.m.in_channels, self.c_lift
+        w0, b0, w1, b1 = lift[0].weight, lift[0].bias, lift[1].weight, lift[1].bias
+        both = self._lift_fused_both(Ch)
         if not both:
             self._wgrad(B, C1, Ch, P0, None, gx, w1, b1, xv=self.a1_virtual)
-        with self._fork():
-            chunks = int(L.lib().ppsci_fno_lift0_wgrad_chunks(B, P0))
-            ld = C1 * K0 + C1
-            part = self._partials(chunks * ld)
-            ld1 = Ch * C1 + Ch
-            part1 = self._partials(chunks * ld1) if both else None
-            assert gx_add is None or both
-            L.check(L.lib().ppsci_fno_lift0_wgrad(B, K0, C1, Ch, P0, _p(self.x_in), _p(w0), _p(b0), _p(w1), _p(gx), _p(gx_add),
-                                                  _p(part), C.c_void_p(part.data_ptr() + 4 * C1 * K0), ld,
-                                                  _p(part1) if both else None, ld1 if both else 0, _stream_ptr(gx)))
-            self._wsegs.append((part.data_ptr(), w0.grad.view(-1).data_ptr(), chunks, ld))
-            if both:
-                self._wsegs.append((part1.data_ptr(), w1.grad.view(-1).data_ptr(), chunks, ld1))
+        chunks = int(L.lib().ppsci_fno_lift0_wgrad_chunks(B, P0))
+        ld = C1 * K0 + C1
+        part = self._partials(chunks * ld)
+        ld1 = Ch * C1 + Ch
+        part1 = self._partials(chunks * ld1) if both else None
+        assert gx_add is None or both
+        L.check(L.lib().ppsci_fno_lift0_wgrad(B, K0, C1, Ch, P0, _p(self.x_in), _p(w0), _p(b0), _p(w1), _p(gx), _p(gx_add),
+                                              _p(part), C.c_void_p(part.data_ptr() + 4 * C1 * K0), ld,
+                                              _p(part1) if both else None, ld1 if both else 0, _stream_ptr(gx)))
+        self._wsegs.append((part.data_ptr(), w0.grad.view(-1).data_ptr(), chunks, ld))
+        if both:
+            self._wsegs.append((part1.data_ptr(), w1.grad.view(-1).data_ptr(), chunks, ld1))
         return True
 
     def _backward(self, gy: torch.Tensor) -> None:
@@ -382,7 +348,7 @@ class FnoNative(NativeExecutor):
         # projection: y = W2 gelu(z2) + b2, z2 = W1 x_out + b1
         self._wgrad(B, self.c_proj, m.out_channels, P0, self.z2, gy, proj[1].weight, proj[1].bias, xv=self.gelu_on_load)
         gz2 = self.gz2
-        if (m.out_channels <= 4 and P0 % 4 == 0 and os.environ.get("PPSCI_FNO_PROJ_STREAMED", "1") != "0"
+        if (m.out_channels <= 4 and P0 % 4 == 0
                 and (gy.data_ptr() | gz2.data_ptr() | self.z2.data_ptr()) % 16 == 0):
             # <= 4 output channels: the hidden gradient is GELU'(z2) times a rank-m factor -- streamed (fno.hip), not a K = m GEMM
             L.check(L.lib().ppsci_fno_proj_hidden_grad(B, self.c_proj, m.out_channels, P0, _p(self.z2), _p(proj[1].weight), _p(gy),
@@ -393,7 +359,7 @@ class FnoNative(NativeExecutor):
         gx = self.gb.view(-1)[:B * Ch * P].view(B, Ch, P)  # dL/d(block output), ping-pongs with `gnext`
         gnext = self.ga.view(-1)[:B * Ch * P].view(B, Ch, P)
         if self.padded:  # the gradient of unpad is pad: zeros outside the window
-            gxu = self.x0u  # (free during the backward pass; NOT xou: the weight gradient above still reads it on the side stream)
+            gxu = self.x0u  # (free during the backward pass)
             _pw_conv(B, self.c_proj, Ch, P0, gz2, proj[0].weight, gxu, transpose=True)
             self._pad(gxu, self.gpad, False)
             gx = self.gpad
@@ -405,7 +371,7 @@ class FnoNative(NativeExecutor):
         gx2_modes = None  # ... or its kept modes: the consumer evaluates the inverse transform itself (fuse_dft)
         for l in range(nl - 1, -1, -1):
             conv, skip = fb.convs[l], fb.fno_skips[l]
-            gt = self.gts[l]
+            gt = self.gt
             nrm = fb.norm[l] if fb.norm is not None else None
             last = l == nl - 1
             if self.kept:  # dL/dv only feeds the spectral branch: its kept modes come out of the tail's second pass, gv is not stored
@@ -446,19 +412,12 @@ class FnoNative(NativeExecutor):
                 L.check(L.lib().ppsci_sht_analysis(B * Ch, H, W, mx, my, _p(self.sht_tw), _p(self.sht_b_an), _p(self.gv), _p(self.ghat), st))
                 L.check(L.lib().ppsci_sht_contract_wgrad(B, Ch, Ch, mx, my, _p(self.xft[l]), _p(self.ghat), _p(conv.weight_real.grad),
                                                          _p(conv.weight_imag.grad), st))
-                if os.environ.get("PPSCI_SHT_FUSE_CONTRACT", "0") == "1":
-                    L.check(L.lib().ppsci_sht_synthesis_contract(B, Ch, Ch, 1, H, W, mx, my, _p(self.sht_tw), _p(self.sht_a_sy),
-                                                                 _p(self.ghat), _p(conv.weight_real), _p(conv.weight_imag), _p(self.gsp), st))
-                else:
-                    L.check(L.lib().ppsci_sht_contract(B, Ch, Ch, mx, my, _p(self.ghat), _p(conv.weight_real), _p(conv.weight_imag), 1,
-                                                       _p(self.gx_ft), st))
-                    L.check(L.lib().ppsci_sht_synthesis(B * Ch, H, W, mx, my, _p(self.sht_tw), _p(self.sht_a_sy), _p(self.gx_ft), _p(self.gsp), st))
+                L.check(L.lib().ppsci_sht_contract(B, Ch, Ch, mx, my, _p(self.ghat), _p(conv.weight_real), _p(conv.weight_imag), 1,
+                                                   _p(self.gx_ft), st))
+                L.check(L.lib().ppsci_sht_synthesis(B * Ch, H, W, mx, my, _p(self.sht_tw), _p(self.sht_a_sy), _p(self.gx_ft), _p(self.gsp), st))
             else:
-                L.check(L.lib().ppsci_fft2d_r2c(B * Ch, H, W, _p(self.gv), _p(self.ghat), st))
-                L.check(L.lib().ppsci_spectral_conv2d_bwd_real_scaled(
-                    C.byref(self.desc), _p(self.xft[l]), _p(conv.weight_real), _p(conv.weight_imag), _p(self.ghat),
-                    _p(self.gx_ft), _p(conv.weight_real.grad), _p(conv.weight_imag.grad), self.inv_n, W, self.inv_n, 1, st))
-                L.check(L.lib().ppsci_fft2d_c2r(B * Ch, H, W, _p(self.gx_ft), _p(self.gsp), st))
+                self._fft_spectral_bwd(self.desc, conv, self.inv_n, self.hw, self.hw, self.gv, self.xft[l], self.ghat, None,
+                                       self.gx_ft, self.gsp)
             if self.stab:  # gnext += gsp * (1 - tanh(x_l)^2)
                 L.check(L.lib().ppsci_tanh_bwd(B * Ch * P, _p(self.xs[l]), _p(self.gsp), _p(gnext), 1, st))
                 gx2 = None
@@ -488,4 +447,3 @@ class FnoNative(NativeExecutor):
                 self._wgrad(B, m.in_channels, self.c_lift, P0, self.x_in, gz1, lift[0].weight, lift[0].bias)
         else:
             self._wgrad(B, m.in_channels, Ch, P0, self.x_in, gx, lift[0].weight, lift[0].bias)
-        self._join()  # every weight gradient's partial rows are complete

@@ -128,6 +128,7 @@ class OperatorEngine:
         # forward and backward on this framework's own kernels, no autograd graph of the network: the model's own executor
         # (native_executor.NativeExecutor), which refuses a model its kernels do not cover with its own reason
         self.native = model.native()
+        self._deferred: Dict[tuple, list] = {}  # step-graph key -> the pending weight-gradient row sums of that key's passes
 
     def _forward_backward_eager(self, constraints: List[OperatorConstraint]):
         if len(constraints) != 1:
@@ -147,24 +148,30 @@ class OperatorEngine:
     def forward_backward_deferred(self, constraints: List[OperatorConstraint]):
         """forward_backward with the sums over the weight-gradient partials left to the caller (one launch together with its
         Adam update, hp.reduce_rows_multi_adam): returns them as (source, destination, rows, cols) pointers."""
+        key = tuple((id(c), c.version) for c in constraints) + (self.native.generation, "deferred")
+
+        def eager():
+            self._forward_backward_eager(constraints)
+            self._deferred[key] = self.native.wgrad_segments
+
         self.native.defer_wgrad_sums = True
         try:
-            key = tuple((id(c), c.version) for c in constraints) + (self.native.generation, "deferred")
-            self._step_graph.run(key, lambda: self._forward_backward_eager(constraints))
+            self._step_graph.run(key, eager)
         finally:
             self.native.defer_wgrad_sums = False
-        # (a replayed graph does not run Python: the segment list of the capturing / eager pass stays valid -- same buffers)
-        segs = self.native.wgrad_segments or self._deferred_segs
-        self._deferred_segs = segs
+        # (a replayed graph does not run Python: the segment list of THIS key's capturing / eager pass stays valid -- same buffers.
+        # Kept in the step graph's own order and number: most recently used last, the oldest out)
+        segs = self._deferred[key] = self._deferred.pop(key)
+        while len(self._deferred) > self._step_graph.max_graphs:
+            self._deferred.pop(next(iter(self._deferred)))
         return segs
-
-    _deferred_segs = None
 
     def flush_deferred(self, segs) -> None:
         self.native.flush_wgrads(segs)
 
     def invalidate_graphs(self) -> None:
         self._step_graph.clear()
+        self._deferred.clear()
 
     def allreduce(self, buf: Optional[torch.Tensor] = None):
         if self.world > 1:

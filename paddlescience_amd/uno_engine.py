@@ -88,13 +88,10 @@ class _Resampler:
 
 
 class UnoNative(FnoNative):
-    """FnoNative's 1x1-convolution calls and weight-gradient partials (`_wgrad`) on this network's own buffers, in one stream."""
+    """FnoNative's 1x1-convolution calls, weight-gradient partials (`_wgrad`) and hipFFT spectral layer (`_fft_spectral[_bwd]`) on
+    this network's own buffers."""
 
     label, supports = "UNO", staticmethod(supports)
-
-    def __init__(self, model):
-        super().__init__(model)
-        self.use_side = False
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int, H0: int, W0: int) -> None:
@@ -158,9 +155,14 @@ class UnoNative(FnoNative):
             scale = 1.0 / float(H2 * W2)
             src = m.horizontal_skips_map.get(i)
             # the transforms on the kept modes only (two small DFTs per plane in LDS, csrc/spectral_conv.hip) when the planes of both
-            # grids fit; hipFFT on full spectra + ppsci_spectrum_resize otherwise (PPSCI_FNO_FULL_FFT=1 forces it: tests, timing)
+            # grids fit every launch this block then issues -- the forward transform on (H, W), the contraction inside the inverse
+            # transform onto (H2, W2), the transform of dL/dv back from (H2, W2), the data gradient's contraction + inverse on (H, W);
+            # hipFFT on full spectra + ppsci_spectrum_resize otherwise (PPSCI_FNO_FULL_FFT=1 forces it: tests, timing)
+            inv_ok = L.lib().ppsci_spectral_conv2d_inv_kept_supported
+            hs, ws = (H, W) if (H, W) != (H2, W2) else (0, 0)
             kept = (bool(L.lib().ppsci_dft2_kept_supported(H, W, d.modes_x, d.modes_y))
                     and bool(L.lib().ppsci_dft2_kept_from_supported(H2, W2, d.modes_x, d.modes_y))
+                    and bool(inv_ok(H2, W2, hs, ws, d.modes_x, d.modes_y)) and bool(inv_ok(H, W, 0, 0, d.modes_x, d.modes_y))
                     and os.environ.get("PPSCI_FNO_FULL_FFT", "0") != "1")
             nk = (d.modes_x, d.modes_y, 2)
             e = dict(
@@ -249,14 +251,7 @@ class UnoNative(FnoNative):
                                                                   _p(conv.weight_real), _p(conv.weight_imag), e["scale"], _p(e["v"]),
                                                                   None, None, st))
             else:
-                L.check(L.lib().ppsci_fft2d_r2c(B * ci, H, W, _p(cur), _p(e["xft"]), st))
-                L.check(L.lib().ppsci_spectral_conv2d_fwd_scaled(C.byref(e["desc"]), _p(e["xft"]), _p(conv.weight_real),
-                                                                 _p(conv.weight_imag), _p(e["out_ft"]), e["scale"], 1, st))
-                zf = e["out_ft"]
-                if e["resized"]:
-                    L.check(L.lib().ppsci_spectrum_resize(B * co, H, W // 2 + 1, H2, W2 // 2 + 1, 0, 0, _p(zf), _p(e["out_ft2"]), st))
-                    zf = e["out_ft2"]
-                L.check(L.lib().ppsci_fft2d_c2r(B * co, H2, W2, _p(zf), _p(e["v"]), st))
+                self._fft_spectral(e["desc"], conv, e["scale"], e["hw"], e["hw2"], cur, e["xft"], e["out_ft"], e["out_ft2"], e["v"])
             nrm = blk.norm[0] if blk.norm is not None else None
             L.check(L.lib().ppsci_fno_tail_fwd(
                 B, co, P2, 1 if nrm is not None else 0, 0, float(nrm.eps) if nrm is not None else 0.0, _p(e["v"]), _p(conv.bias),
@@ -345,17 +340,8 @@ class UnoNative(FnoNative):
                 L.check(L.lib().ppsci_spectral_conv2d_inv_kept_ex(C.byref(e["desc"]), H, W, 0, 0, 3, 0, _p(ghat), _p(conv.weight_real),
                                                                   _p(conv.weight_imag), e["scale"], _p(gxin), None, None, st))
             else:
-                ghat = V(self.gf[0], B, co, H2, Wf2, 2)
-                L.check(L.lib().ppsci_fft2d_r2c(B * co, H2, W2, _p(gv), _p(ghat), st))
-                G = ghat
-                if e["resized"]:
-                    G = V(self.gf[1], B, co, H, Wf, 2)
-                    L.check(L.lib().ppsci_spectrum_resize(B * co, H2, Wf2, H, Wf, W2, W, _p(ghat), _p(G), st))
-                gx_ft = V(self.gf[2], B, ci, H, Wf, 2)
-                L.check(L.lib().ppsci_spectral_conv2d_bwd_real_scaled(
-                    C.byref(e["desc"]), _p(e["xft"]), _p(conv.weight_real), _p(conv.weight_imag), _p(G), _p(gx_ft),
-                    _p(conv.weight_real.grad), _p(conv.weight_imag.grad), e["scale"], W, e["scale"], 1, st))
-                L.check(L.lib().ppsci_fft2d_c2r(B * ci, H, W, _p(gx_ft), _p(gsp), st))
+                self._fft_spectral_bwd(e["desc"], conv, e["scale"], e["hw"], e["hw2"], gv, e["xft"], V(self.gf[0], B, co, H2, Wf2, 2),
+                                       V(self.gf[1], B, co, H, Wf, 2), V(self.gf[2], B, ci, H, Wf, 2), gsp)
                 hp.reduce_rows(gsp.view(1, -1), 1, B * ci * P, gxin.view(-1), True)  # gxin += gsp
             # the input was concat(previous output, U skip): split the gradient
             if e["src"] is not None:

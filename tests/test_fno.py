@@ -112,3 +112,60 @@ def test_transforms_on_the_kept_modes(n, H, W, modes, dev):
         L.check(lib.ppsci_dft2_kept_inv(n, H, W, mx, my, which, _p(Z), _p(y), _stream_ptr(y)))
         assert rel(y.cpu().numpy(), yref.numpy()) < 2e-6, which
 
+
+@pytest.mark.parametrize("stats", [False, True])
+@pytest.mark.parametrize("H,W,modes", [(16, 16, (8, 5)), (9, 7, (4, 3))])
+def test_contraction_inside_the_inverse_transform_equals_the_two_launches(H, W, modes, stats, dev):
+    """ppsci_spectral_conv2d_inv_kept (the forward contraction inside the inverse transform's launch) against
+    ppsci_spectral_conv2d_fwd_kept + ppsci_dft2_kept_inv, and -- stats: with sbias and rows_out -- + ppsci_dft2_kept_inv_stats: the
+    same y up to the order of the channel sum (rel-L2 < 1e-6), on random spectra and weights, B = 2, 6 -> 5 channels; 9 x 7: odd H,
+    where the rows of the output spectrum are not those of the input's.
+    The three statistics columns of rows_out ([0] the fp32 row mean mr, [1] sum (u - mr)^2, [2] sum (u - mr), u = y + sbias) are
+    compared at the rule of tests/test_fno_tail.py: within max(4 x e32, 5e-7), e32 = the error of the same statistic evaluated in
+    plain float32 against float64 on these planes.  [2] is a rounding residue about mr, so -- as that file measures gsbias, the other
+    cancellation -- its difference is taken against sum |u - mr|, not against its own norm."""
+    from paddlescience_amd.device import get_device
+
+    d = get_device()
+    mx, my = modes
+    B, ci, co, P = 2, 6, 5, H * W
+    lib = L.lib()
+    assert lib.ppsci_spectral_conv2d_inv_kept_supported(H, W, 0, 0, mx, my) == 1
+    rng = np.random.default_rng(H + W + stats)
+    t = lambda *sh: torch.as_tensor(rng.standard_normal(sh).astype(np.float32)).to(d)  # noqa: E731
+    xk, wr, wi, sb = t(B, ci, mx, my, 2), t(ci, co, mx, my), t(ci, co, mx, my), 0.5 * t(co)
+    desc = L.SpectralDesc()
+    desc.batch, desc.c_in, desc.c_out, desc.h, desc.wf, desc.modes_x, desc.modes_y = B, ci, co, H, W // 2 + 1, mx, my
+    scale = 1.0 / P
+    nan = lambda *sh: torch.full(sh, float("nan"), dtype=torch.float32, device=d)  # noqa: E731
+    zk, y2, y1, rows2, rows1 = nan(B, co, mx, my, 2), nan(B * co, P), nan(B * co, P), nan(B * co, 4), nan(B * co, 4)
+    st = _stream_ptr(y1)
+    L.check(lib.ppsci_spectral_conv2d_fwd_kept(C.byref(desc), _p(xk), _p(wr), _p(wi), _p(zk), scale, st))
+    if stats:
+        L.check(lib.ppsci_dft2_kept_inv_stats(B * co, H, W, mx, my, 1, _p(zk), _p(y2), _p(sb), co, _p(rows2), st))
+    else:
+        L.check(lib.ppsci_dft2_kept_inv(B * co, H, W, mx, my, 1, _p(zk), _p(y2), st))
+    L.check(lib.ppsci_spectral_conv2d_inv_kept(C.byref(desc), H, W, 1, _p(xk), _p(wr), _p(wi), scale, _p(y1),
+                                               _p(sb) if stats else None, _p(rows1) if stats else None, st))
+    assert torch.isfinite(y1).all() and torch.isfinite(y2).all()
+    e = rel(y1.cpu().numpy(), y2.cpu().numpy())
+    print(f"inv_kept {H} x {W} stats={stats}: y rel-L2 {e:.3e}")
+    assert e < 1e-6
+    if not stats:
+        return
+    u = y2.cpu() + sb.cpu().repeat(B)[:, None]  # float32, what both references below read
+    u64, mr32 = u.double(), u.mean(1)
+    dev64 = u64 - mr32.double()[:, None]
+    dev32 = u - mr32[:, None]
+    scale2 = float(dev64.abs().sum())
+    e32 = (rel(mr32.numpy(), u64.mean(1).numpy()), rel((dev32 * dev32).sum(1).numpy(), (dev64 * dev64).sum(1).numpy()),
+           float((dev32.sum(1).double() - dev64.sum(1)).abs().sum()) / scale2)
+    r1, r2 = rows1.cpu().double(), rows2.cpu().double()
+    assert torch.isfinite(r1[:, :3]).all() and torch.isfinite(r2[:, :3]).all()
+    got = (rel(r1[:, 0].numpy(), r2[:, 0].numpy()), rel(r1[:, 1].numpy(), r2[:, 1].numpy()),
+           float((r1[:, 2] - r2[:, 2]).abs().sum()) / scale2)
+    for k in range(3):
+        bound = max(4.0 * e32[k], 5e-7)
+        print(f"inv_kept {H} x {W} rows_out[{k}]: difference {got[k]:.3e} fp32-ref {e32[k]:.3e} bound {bound:.3e}")
+        assert got[k] <= bound, k
+

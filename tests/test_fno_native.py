@@ -32,26 +32,74 @@ def _padding(c):
     return ([fh, fw] if fh or fw else None), ("symmetric" if sym else "one-sided")
 
 
-@pytest.mark.parametrize("c", CASES[:2])
-def test_contraction_inside_the_inverse_transform_equals_the_two_launches(c, dev, monkeypatch):
-    """ppsci_spectral_conv2d_inv_kept (the forward contraction inside the inverse transform's launch, with or without the tail's row
-    sums) against ppsci_spectral_conv2d_fwd_kept + ppsci_dft2_kept_inv[_stats]: the same output up to the order of the channel sum."""
+def _against_the_oracle(model, modes, B, H, W, seed):
+    """One forward + backward of the model's executor on a random batch against the fp64 restatement (oracle/ref_torch.fno_forward):
+    (the executor, output rel-L2, flat-gradient rel-L2); every gradient entry must have been written."""
     import ppsci
-    from paddlescience_amd.fno_engine import FnoNative
+    from oracle import ref_torch as R
 
-    (mx, my, hid, lift, proj, nl, norm), P, _ = _case(c)
-    pad, pad_mode = _padding(c)
-    outs = []
-    for fuse in ("1", "0"):
-        monkeypatch.setenv("PPSCI_FNO_FUSE_CONTRACT", fuse)
-        model = ppsci.arch.TFNO2dNet(("x",), ("y",), mx, my, hid, 3, 1, lift, proj, nl, norm=norm, domain_padding=pad,
-                                     domain_padding_mode=pad_mode)
-        model.set_state_dict({k: v.astype(np.float32) for k, v in P.items()})
-        eng = FnoNative(model)
-        x = torch.as_tensor(G[f"{c}/x"].astype(np.float32)).to(model.flat_params.device)
-        outs.append(eng.forward(x).detach().cpu().numpy().copy())
-        assert eng.fuse_contract == (fuse == "1" and eng.kept)
-    assert rel(outs[0], outs[1]) < 1e-6
+    d = model.flat_params.device
+    rng = np.random.default_rng(seed)
+    x = torch.as_tensor(rng.standard_normal((B, model.in_channels, H, W)).astype(np.float32)).to(d)
+    tgt = torch.as_tensor(rng.standard_normal((B, model.out_channels, H, W)).astype(np.float32)).to(d)
+    P = {n: p.detach().cpu().double().requires_grad_(True) for n, p in torch.nn.Module.named_parameters(model)}
+    yo = R.fno_forward(x.cpu().double(), P, model.n_layers, modes, "group_norm")
+    lo = ((yo - tgt.cpu().double()) ** 2).mean()
+    go = np.concatenate([g.numpy().ravel() for g in torch.autograd.grad(lo, [P[n] for n, _ in torch.nn.Module.named_parameters(model)])])
+    eng = model.native()
+    y = eng.forward(x)
+    _, gy = ppsci.loss.MSELoss("mean").value_and_grad(y, tgt, "y")
+    model.flat_grad.fill_(float("nan"))
+    eng.backward(gy)
+    assert torch.isfinite(model.flat_grad).all()
+    ey, eg = rel(y.cpu().numpy(), yo.detach().numpy()), rel(model.flat_grad.cpu().numpy(), go)
+    print(f"output rel-L2 {ey:.3e}, gradient rel-L2 {eg:.3e}")
+    return eng, ey, eg
+
+
+def test_plane_that_fits_the_transforms_but_not_the_fused_contraction_takes_the_library_path(dev):
+    """A 44 x 44 plane with ALL its 44 x 23 modes kept fits the stand-alone kept-mode transforms and the block tails
+    (ppsci_dft2_kept_supported) but not the contraction inside the inverse transform, whose launch holds the parts of the channel
+    sum next to the inverse stages: 66112 B of LDS.  The executor has to see that before it plans the blocks (the launch refused
+    the shape at the first forward once) and run hipFFT on the full spectrum -- against the fp64 restatement at this file's bounds."""
+    import ppsci
+    from paddlescience_amd import _lib as L
+
+    assert L.lib().ppsci_dft2_kept_supported(44, 44, 44, 23) == 1
+    assert L.lib().ppsci_spectral_conv2d_inv_kept_supported(44, 44, 0, 0, 44, 23) == 0
+    assert L.lib().ppsci_spectral_conv2d_inv_kept_supported(64, 64, 0, 0, 12, 7) == 1
+    torch.manual_seed(11)
+    model = ppsci.arch.FNONet(("x",), ("y",), (44, 44), 4, 3, 1, 8, 8, 1, norm="group_norm")
+    eng, ey, eg = _against_the_oracle(model, (44, 44), 1, 44, 44, 6)
+    assert eng.kept is False
+    assert ey < 1e-5
+    assert eg < 2e-4
+
+
+#   (cin, hidden, cout)   lifting hidden tensor   first-layer gradient fused   ... and the second   (projection: streamed for cout <= 4)
+LIFT_PROJ_ROUTES = [((5, 8, 1), False, False, False),   # stored lifting hidden tensor (more than 4 input channels)
+                    ((3, 6, 1), True, False, False),    # virtual, two-launch gradients: hidden not a multiple of 4
+                    ((3, 68, 1), True, False, False),   # virtual, two-launch gradients: hidden above 64
+                    ((3, 36, 1), True, True, False),    # fused first-layer gradient, the second layer's separate (hidden above 32)
+                    ((3, 8, 5), True, True, True)]      # both fused; 5 output channels: the projection's hidden gradient is a GEMM
+
+
+@pytest.mark.parametrize("chans,virtual,lift0,both", LIFT_PROJ_ROUTES)
+def test_shape_selects_the_lifting_and_projection_kernels(dev, chans, virtual, lift0, both):
+    """Every route the shape of the two channel MLPs can select in the backward pass (fno_engine.FnoNative: the lifting's hidden
+    tensor stored or recomputed on load, ppsci_fno_lift0_wgrad for one or both lifting gradients or the two-launch path,
+    ppsci_fno_proj_hidden_grad or the K = cout GEMM), each against the fp64 restatement at this file's bounds."""
+    import ppsci
+
+    cin, hidden, cout = chans
+    torch.manual_seed(7)
+    model = ppsci.arch.FNONet(("x",), ("y",), (4, 4), hidden, cin, cout, 10, 12, 2, norm="group_norm")
+    eng, ey, eg = _against_the_oracle(model, (4, 4), 2, 8, 8, 8)
+    assert eng.lift_virtual is virtual
+    assert eng._lift0_fusable(hidden) is lift0
+    assert eng._lift_fused_both(hidden) is both
+    assert ey < 1e-5
+    assert eg < 2e-4
 
 
 @pytest.mark.parametrize("full_fft", [False, True])

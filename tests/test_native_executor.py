@@ -136,7 +136,7 @@ def test_unsupported_model_is_refused_with_the_hook_s_reason():
 
 
 @pytest.mark.parametrize("module, cls, label, extra", [
-    ("fno_engine", "FnoNative", "FNO", {"use_side", "_side"}), ("uno_engine", "UnoNative", "UNO", {"use_side", "_side"}),
+    ("fno_engine", "FnoNative", "FNO", set()), ("uno_engine", "UnoNative", "UNO", set()),
     ("lno_engine", "LnoNative", "LNO", set()), ("geofno_engine", "Fno1dNative", "FNO1d", set())])
 def test_real_executors_declare_the_base_s_attributes(module, cls, label, extra):
     import importlib
@@ -149,6 +149,59 @@ def test_real_executors_declare_the_base_s_attributes(module, cls, label, extra)
     assert not {"_wbufs", "_wcall"} & set(E.EXECUTOR_ATTRS)  # device memory of one shape: per set
     assert set(E.EXECUTOR_ATTRS) - set(NativeExecutor.EXECUTOR_ATTRS) == extra
     assert "_switch" not in E.__dict__ and "backward" not in E.__dict__ and "flush_wgrads" not in E.__dict__
+
+
+def test_deferred_segments_belong_to_the_step_graph_key_that_left_them():
+    """OperatorEngine.forward_backward_deferred after a REPLAY (no Python runs, the executor still holds the last eager pass's list):
+    the segments of the pass that was run under that key, not of whichever pass ran last."""
+    from paddlescience_amd.operator_engine import OperatorEngine
+
+    class _Executor:
+        generation, defer_wgrad_sums, wgrad_segments = 0, False, []
+
+    class _Constraint:
+        version = 0
+
+        def __init__(self, segs):
+            self.segs = segs
+
+        def forward_backward_native(self, native):
+            assert native.defer_wgrad_sums is True
+            native.wgrad_segments = list(self.segs)
+
+    class _Graphs:
+        """A step graph that runs a key's first call and "replays" every later one."""
+        max_graphs = 16
+
+        def __init__(self):
+            self.seen, self.ran = set(), []
+
+        def run(self, key, eager):
+            if key not in self.seen:
+                self.seen.add(key)
+                eager()
+                self.ran.append(key)
+
+        def clear(self):
+            self.seen.clear()
+
+    class _Net:
+        flat_grad = torch.zeros(1)
+
+        def native(self):
+            return _Executor()
+
+    eng = OperatorEngine(_Net())
+    eng._step_graph = graphs = _Graphs()
+    SA, SB = [(1, 2, 3, 4)], [(5, 6, 7, 8), (9, 10, 11, 12)]
+    a, b = _Constraint(SA), _Constraint(SB)
+    assert eng.forward_backward_deferred([a]) == SA
+    assert eng.forward_backward_deferred([b]) == SB
+    assert eng.forward_backward_deferred([a]) == SA and len(graphs.ran) == 2  # (replayed: b's list is what the executor holds)
+    assert eng.forward_backward_deferred([b]) == SB and eng.native.defer_wgrad_sums is False
+    eng.invalidate_graphs()  # the graphs go, and with them what was recorded for their keys
+    a.segs = [(13, 14, 15, 16)]
+    assert eng.forward_backward_deferred([a]) == [(13, 14, 15, 16)] and len(graphs.ran) == 3
 
 
 @pytest.fixture
