@@ -44,7 +44,7 @@ def _refuse_separable(what: str, ys) -> None:
 
 class Jacobians:
     def __init__(self):
-        self.Js: Dict[Tuple[int, int], Sym] = {}
+        self.Js: Dict[Tuple[int, int], tuple] = {}
 
     def _one(self, ys: Sym, x: Sym, i: int, j: Optional[int]) -> Sym:
         _check_x(x)
@@ -53,9 +53,9 @@ class Jacobians:
         if j is not None and not 0 <= j < 1:
             raise ValueError(f"j({j}) should in range [0, 1).")
         key = (id(ys), id(x))
-        if key not in self.Js:
-            self.Js[key] = diff(ys, x.name)
-        return self.Js[key]
+        if key not in self.Js:  # (the entry holds its operands: the ids of a key are not reused while it exists)
+            self.Js[key] = (diff(ys, x.name), ys, x)
+        return self.Js[key][0]
 
     def __call__(self, ys: Sym, xs: Union[Sym, List[Sym]], i: int = 0, j: Optional[int] = None,
                  retain_graph: Optional[bool] = None, create_graph: bool = True):
@@ -73,7 +73,7 @@ class Jacobians:
 
 class Hessians:
     def __init__(self, jac: Jacobians):
-        self.Hs: Dict[Tuple[int, int, Optional[int]], Sym] = {}
+        self.Hs: Dict[Tuple[int, int, Optional[int]], tuple] = {}
         self._jac = jac
 
     def __call__(self, ys: Sym, xs: Sym, component: Optional[int] = None, i: int = 0, j: int = 0,
@@ -85,8 +85,8 @@ class Hessians:
         if key not in self.Hs:
             if grad_y is None:
                 grad_y = self._jac(ys, xs, i=0, j=None)
-            self.Hs[key] = grad_y
-        return self._jac(self.Hs[key], xs, i, j)
+            self.Hs[key] = (grad_y, ys, xs)
+        return self._jac(self.Hs[key][0], xs, i, j)
 
     def _clear(self):
         self.Hs = {}

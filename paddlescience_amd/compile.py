@@ -6,6 +6,7 @@ This is the counterpart of `Solver.__init__`'s `convert_expr` (/root/reference/p
 what the reference re-executes op by op every iteration is decided here once."""
 from __future__ import annotations
 
+import dataclasses
 import os
 import zlib
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -14,6 +15,7 @@ import numpy as np
 import sympy as sp
 import torch
 
+from . import _lib as L
 from . import autodiff, graph
 from .engine import FusedConstraint
 from .graph import Sym
@@ -74,6 +76,99 @@ def _csr_to_dev(M, dev) -> dict:
     return dict(M=up(M), MT=up(M.transpose()))
 
 
+def loss_terms(label_keys: Sequence[str], weight_keys: Sequence[str], loss, n_global: int, input_keys: Sequence[str] = (),
+               rows: Optional[Dict[str, int]] = None, scale: Optional[float] = None) -> List[graph.LossTerm]:
+    """The loss rows graph.lower takes, one per label key under `loss` (None: value rows of scale 0): label / weight / causal
+    columns under their prefixes, an "area" input as the area column.  rows: keys whose mean is over that many samples instead
+    of n_global (batch-coupled outputs); scale: one given scale for every term instead of the loss's own."""
+    def term_scale(k):
+        if scale is not None:
+            return scale
+        return loss.term_scale(k, (rows or {}).get(k, n_global)) if loss is not None else 0.0
+
+    return [graph.LossTerm(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None,
+                           area="area" if "area" in input_keys else None, scale=term_scale(k), kind=getattr(loss, "term_kind", 0),
+                           causal=(CAUSAL_PREFIX + k) if getattr(loss, "causal", None) else None,
+                           periodic=bool(getattr(loss, "periodic", False))) for k in label_keys]
+
+
+@dataclasses.dataclass
+class ConstraintFront:
+    """The device-free half of a CompiledConstraint: the lowering and what bind() needs to know about the outputs."""
+    low: graph.Lowered
+    loss_terms: List[graph.LossTerm]
+    row_slices: Dict[str, int]  # output `expr[a:a+1]` -> a
+    coupled: Dict[str, int]  # batch-coupled output -> its residual rows
+    specialised_to: List[str]  # the value requests the expressions made of the static batch
+
+
+def lower_constraint(model, exprs: Dict[str, Callable], input_keys: Sequence[str], label_keys: Sequence[str],
+                     weight_keys: Sequence[str], loss, batch_size: int, n_global: int, extra_outputs: Sequence[str] = (),
+                     extra_parameters: Sequence = (), static_batch: Optional[Dict[str, object]] = None) -> ConstraintFront:
+    """Everything a constraint decides before it owns device memory: the trace, row-sliced and batch-coupled outputs, labels
+    on raw network outputs, the loss terms and graph.lower.  tools/gen_static_programs.py calls it too, so the compile-time
+    tables are made from what a constraint runs."""
+    # static_batch: the input columns of the one batch this constraint will ever be bound to; the value requests the
+    # expressions made of it (`if float(d["x"][0]) == 0.0:` ...) -- non-empty: the program is specialised to that batch
+    specialised_to: List[str] = []
+    outputs = trace_exprs(model, input_keys, exprs, extra_parameters, static_batch, specialised_to)
+    # Row slices `expr[a:a+1]` as whole outputs (examples/euler_beam/euler_beam.py:49-54).  The reference's loss then
+    # broadcasts the [1, 1] value against the [n, 1] label / weight columns (mse.py:82-105):
+    #     sum_p w_p (v_a - l_p)^2  =  W (v_a - lbar)^2 + const,   W = sum w_p,  lbar = sum w_p l_p / W,
+    # i.e. a per-point loss on row a alone with label lbar and weight W -- which IS a per-point program: at bind time the
+    # label column becomes lbar, the weight column a one-hot W at row a, and const is added to the reported term.
+    row_slices: Dict[str, int] = {}
+    for k, v in list(outputs.items()):
+        if isinstance(v, Sym) and v.kind == "rows":
+            a, b = v.comp
+            b = batch_size if b is None else b
+            if (a, b) == (0, batch_size):
+                outputs[k] = v.args[0]
+                continue
+            simple = (b - a == 1 and 0 <= a < batch_size and k in label_keys and loss is not None
+                      and getattr(loss, "term_kind", 0) == 0 and not getattr(loss, "causal", None)
+                      and not getattr(loss, "periodic", False) and n_global == batch_size)
+            if not simple:
+                raise NotImplementedError(f"row slice [{a}:{b}] of output {k!r}: only one-row slices under MSELoss on a "
+                                          "single rank are lowered to the fused kernels")
+            row_slices[k] = a
+            outputs[k] = v.args[0]
+    weight_keys = list(weight_keys) + [k for k in row_slices if k not in weight_keys]
+    # Batch-coupled outputs (graph.couple: Volterra's `lhs[:N] - int_mat @ u`): the residual exists on the first R rows of
+    # the batch only -- the label / weight columns of the reference have R rows (volterra_ide.py: the dataset transform grows
+    # the INPUT to N + N Q quadrature points) and the loss is a mean over R.  Here: columns padded to the batch with a zero
+    # weight behind row R (bind), the term scale taken for R samples.
+    coupled: Dict[str, int] = {k: v.comp[0] for k, v in outputs.items() if isinstance(v, Sym) and v.kind == "couple"}
+    for k, v in outputs.items():
+        if k in coupled:
+            if v.comp[1] != batch_size or n_global != batch_size:
+                raise NotImplementedError(f"batch-coupled output {k!r}: its matrix has {v.comp[1]} columns for a batch of "
+                                          f"{batch_size} points" + (" (single rank only)" if n_global != batch_size else ""))
+            if k not in label_keys or loss is None or getattr(loss, "term_kind", 0) != 0:
+                raise NotImplementedError(f"batch-coupled output {k!r} is lowered as an MSELoss term")
+    weight_keys = weight_keys + [k for k in coupled if k not in weight_keys]
+    for k in label_keys:
+        if k not in outputs:
+            # a label on a raw network output (expression.py: output_dict holds the model outputs too)
+            if k in model.output_keys:
+                outputs[k] = Sym.net(model, model.output_keys.index(k))
+            else:
+                raise KeyError(f"label key {k!r} is neither an expression nor a network output")
+    terms = loss_terms(label_keys, weight_keys, loss, n_global, input_keys, rows=coupled)
+    low = graph.lower(outputs, terms, extra_outputs, n_global=n_global)
+    if getattr(loss, "periodic", False):
+        if batch_size % 2:
+            raise ValueError(f"Length of output({batch_size}) should be even.")  # mse.py:326-329
+        if any(k in weight_keys for k in label_keys):
+            raise ValueError("Periodic*Loss with per-point weights: the reference multiplies its [n] pair terms by the "
+                             "[2n] weight column, which does not broadcast (mse.py:335-336)")
+    causal = getattr(loss, "causal", None)
+    if causal and batch_size % int(causal["n_chunks"]) != 0:
+        raise ValueError(f"CausalMSELoss: batch size {batch_size} is not a multiple of n_chunks "
+                         f"{causal['n_chunks']} (loss.reshape([n_chunks, -1]), mse.py:168)")
+    return ConstraintFront(low, terms, row_slices, coupled, specialised_to)
+
+
 class CompiledConstraint:
     """A constraint (or validator) bound to the fused kernels for a fixed batch size."""
 
@@ -82,72 +177,10 @@ class CompiledConstraint:
                  device, train: bool = True, want_values: bool = False, extra_outputs: Sequence[str] = (),
                  extra_parameters: Sequence = (), static_batch: Optional[Dict[str, object]] = None):
         self.name, self.model, self.loss = name, model, loss
-        # static_batch: the input columns of the one batch this constraint will ever be bound to; the value requests the
-        # expressions made of it (`if float(d["x"][0]) == 0.0:` ...) -- non-empty: the program is specialised to that batch
-        self.specialised_to: List[str] = []
-        outputs = trace_exprs(model, input_keys, exprs, extra_parameters, static_batch, self.specialised_to)
-        # Row slices `expr[a:a+1]` as whole outputs (examples/euler_beam/euler_beam.py:49-54).  The reference's loss then
-        # broadcasts the [1, 1] value against the [n, 1] label / weight columns (mse.py:82-105):
-        #     sum_p w_p (v_a - l_p)^2  =  W (v_a - lbar)^2 + const,   W = sum w_p,  lbar = sum w_p l_p / W,
-        # i.e. a per-point loss on row a alone with label lbar and weight W -- which IS a per-point program: at bind time the
-        # label column becomes lbar, the weight column a one-hot W at row a, and const is added to the reported term.
-        self._row_slices: Dict[str, int] = {}
-        for k, v in list(outputs.items()):
-            if isinstance(v, Sym) and v.kind == "rows":
-                a, b = v.comp
-                b = batch_size if b is None else b
-                if (a, b) == (0, batch_size):
-                    outputs[k] = v.args[0]
-                    continue
-                simple = (b - a == 1 and 0 <= a < batch_size and k in label_keys and loss is not None
-                          and getattr(loss, "term_kind", 0) == 0 and not getattr(loss, "causal", None)
-                          and not getattr(loss, "periodic", False) and n_global == batch_size)
-                if not simple:
-                    raise NotImplementedError(f"row slice [{a}:{b}] of output {k!r}: only one-row slices under MSELoss on a "
-                                              "single rank are lowered to the fused kernels")
-                self._row_slices[k] = a
-                outputs[k] = v.args[0]
-        weight_keys = list(weight_keys) + [k for k in self._row_slices if k not in weight_keys]
-        # Batch-coupled outputs (graph.couple: Volterra's `lhs[:N] - int_mat @ u`): the residual exists on the first R rows of
-        # the batch only -- the label / weight columns of the reference have R rows (volterra_ide.py: the dataset transform grows
-        # the INPUT to N + N Q quadrature points) and the loss is a mean over R.  Here: columns padded to the batch with a zero
-        # weight behind row R (bind), the term scale taken for R samples.
-        self._coupled: Dict[str, int] = {k: v.comp[0] for k, v in outputs.items() if isinstance(v, Sym) and v.kind == "couple"}
-        for k, v in outputs.items():
-            if k in self._coupled:
-                if v.comp[1] != batch_size or n_global != batch_size:
-                    raise NotImplementedError(f"batch-coupled output {k!r}: its matrix has {v.comp[1]} columns for a batch of "
-                                              f"{batch_size} points" + (" (single rank only)" if n_global != batch_size else ""))
-                if k not in label_keys or loss is None or getattr(loss, "term_kind", 0) != 0:
-                    raise NotImplementedError(f"batch-coupled output {k!r} is lowered as an MSELoss term")
-        weight_keys = weight_keys + [k for k in self._coupled if k not in weight_keys]
-        for k in label_keys:
-            if k not in outputs:
-                # a label on a raw network output (expression.py: output_dict holds the model outputs too)
-                if k in model.output_keys:
-                    outputs[k] = Sym.net(model, model.output_keys.index(k))
-                else:
-                    raise KeyError(f"label key {k!r} is neither an expression nor a network output")
-        losses = []
-        for k in label_keys:
-            losses.append(dict(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None,
-                               area="area" if "area" in input_keys else None,
-                               scale=loss.term_scale(k, self._coupled.get(k, n_global)) if loss is not None else 0.0,
-                               kind=getattr(loss, "term_kind", 0) if loss is not None else 0,
-                               causal=(CAUSAL_PREFIX + k) if getattr(loss, "causal", None) else None,
-                               periodic=bool(getattr(loss, "periodic", False))))
-        self._loss_rows = losses
-        self.low = graph.lower(outputs, losses, extra_outputs, n_global=n_global)
-        if getattr(loss, "periodic", False):
-            if batch_size % 2:
-                raise ValueError(f"Length of output({batch_size}) should be even.")  # mse.py:326-329
-            if any(k in weight_keys for k in label_keys):
-                raise ValueError("Periodic*Loss with per-point weights: the reference multiplies its [n] pair terms by the "
-                                 "[2n] weight column, which does not broadcast (mse.py:335-336)")
-        causal = getattr(loss, "causal", None)
-        if causal and batch_size % int(causal["n_chunks"]) != 0:
-            raise ValueError(f"CausalMSELoss: batch size {batch_size} is not a multiple of n_chunks "
-                             f"{causal['n_chunks']} (loss.reshape([n_chunks, -1]), mse.py:168)")
+        front = lower_constraint(model, exprs, input_keys, label_keys, weight_keys, loss, batch_size, n_global, extra_outputs,
+                                 extra_parameters, static_batch)
+        self.low, self._loss_rows, self.specialised_to = front.low, front.loss_terms, front.specialised_to
+        self._row_slices, self._coupled = front.row_slices, front.coupled
         self.batch_size = batch_size
         self.label_keys = list(label_keys)
         dev = device
@@ -165,7 +198,8 @@ class CompiledConstraint:
         # operator nets (arch/deeponet.py): every branch key is an [N, m] device tensor of its own, handed to the executor
         # through the layout -- never a row of the block above (the epilogue program does not read it)
         self._branch: Dict[str, torch.Tensor] = {}
-        for m, spec, _, idx, pre in self.low.nets:
+        for slot in self.low.nets:
+            m, pre = slot.model, slot.pre
             lay = m.layout
             cols = getattr(m, "branch_cols", None)
             if cols:
@@ -174,14 +208,11 @@ class CompiledConstraint:
                         self._branch[k] = torch.zeros((batch_size, c), dtype=torch.float32, device=dev)
                 lay = lay.with_branch({k: self._branch[k] for k in cols})
             if pre is not None:  # input transform: every network input is an [S, N] stream block
-                import dataclasses
-
-                from . import _lib as L_
-
-                if any(e_ != L_.EMBED_NONE for e_ in (lay.embed or [])):
+                if any(e_ != L.EMBED_NONE for e_ in (lay.embed or [])):
                     raise NotImplementedError("periods together with a registered input transform")
-                lay = dataclasses.replace(lay, embed=[L_.EMBED_STREAMS] * lay.d_raw, omega=[0.0] * lay.d_raw)
-            nets.append((lay, getattr(m, "_param_offset", 0), spec, idx, [(pg.build(), r0, nr) for pg, r0, nr in pre] if pre else None))
+                lay = dataclasses.replace(lay, embed=[L.EMBED_STREAMS] * lay.d_raw, omega=[0.0] * lay.d_raw)
+            nets.append((lay, getattr(m, "_param_offset", 0), slot.spec, slot.inputs,
+                         [(pg.build(), r0, nr) for pg, r0, nr in pre] if pre else None))
         if not nets:
             raise NotImplementedError("a constraint that evaluates no network has nothing to train")
         self.fused = FusedConstraint(name, nets, self.low.streams, self.low.program.build(), inputs, aux,
@@ -195,21 +226,21 @@ class CompiledConstraint:
             if self.low.periodic or self.low.causal or self._row_slices:
                 raise NotImplementedError("batch couplings together with a periodic / causal loss or row-sliced outputs")
             cpl = self.low.couplings
-            mats = []
-            for it in cpl["items"]:
-                M = graph.take_coupling(it["name"])
-                # sparse: M and M^T uploaded once as device CSR (the transposed product is a CSR product of its own)
-                mats.append(_csr_to_dev(M, dev) if isinstance(M, graph.CsrMatrix) else torch.as_tensor(M).to(dev))
-            self.fused.set_couplings(cpl["items"], cpl["pv"].build(), cpl["p3"].build(), mats)
+            # sparse: M and M^T uploaded once as device CSR (the transposed product is a CSR product of its own)
+            mats = [_csr_to_dev(it.matrix, dev) if isinstance(it.matrix, graph.CsrMatrix) else torch.as_tensor(it.matrix).to(dev)
+                    for it in cpl.items]
+            # (uploaded: nothing reachable from the constraint keeps the host copy -- FractionalPoisson's is hundreds of MB)
+            cpl = self.low.couplings = dataclasses.replace(cpl, items=tuple(dataclasses.replace(it, matrix=None) for it in cpl.items))
+            self.fused.set_couplings(cpl.items, cpl.pv.build(), cpl.p3.build(), mats)
         if self.low.reductions:
             if self.low.periodic or self.low.causal or self._row_slices:
                 raise NotImplementedError("batch reductions together with a periodic / causal loss or row-sliced outputs")
             red = self.low.reductions
-            self.fused.set_reductions(red["p1"].build(), red["p3"].build(), red["k"])
+            self.fused.set_reductions(red.p1.build(), red.p3.build(), red.k)
         if self.low.periodic:
             self.fused.set_periodic(self.low.periodic)
         if self.low.causal:
-            self.fused.set_causal(self.low.causal, int(causal["n_chunks"]), float(causal["tol"]))
+            self.fused.set_causal(self.low.causal, int(loss.causal["n_chunks"]), float(loss.causal["tol"]))
         self.train = train
 
     def bind(self, input: Dict[str, object], label: Optional[Dict[str, object]], weight: Optional[Dict[str, object]]):
@@ -325,7 +356,7 @@ class CompiledConstraint:
             col[a] = W / area[a] if area[a] != 0.0 else 0.0
             label[k] = np.full((n, 1), lbar, np.float32)
             weight[k] = col.reshape(n, 1)
-            scale = next(float(r["scale"]) for r in self._loss_rows if r["key"] == k)
+            scale = next(float(r.scale) for r in self._loss_rows if r.key == k)
             offsets[k] = scale * const
         self.fused.loss_offsets = offsets
         # (the cache holds the source objects too, so that their ids cannot be recycled while it is valid)

@@ -44,7 +44,8 @@ class FusedConstraint:
     """Device-resident state of one constraint batch: inputs, aux arrays, streams, stash, partials.
 
     `nets`: one entry per network the constraint evaluates -- (layout, offset of its parameters in the flat
-    parameter buffer, StreamSpec in its own input order, indices of its inputs among `inputs`); a plain layout stands
+    parameter buffer, StreamSpec in its own input order, indices of its inputs among `inputs`, and -- optional, for a
+    registered input transform -- its stream programs as (EpilogueDesc, first feature row, rows)); a plain layout stands
     for a single network at offset 0 that takes all inputs.  The members' streams are consecutive row blocks of U."""
 
     def __init__(self, name: str, nets, streams: hp.StreamSpec, edesc: L.EpilogueDesc,
@@ -158,9 +159,10 @@ class FusedConstraint:
             dist.all_reduce(self.red_values[L.MAX_EPARAM:], op=dist.ReduceOp.SUM)
         hp.epilogue(rd["p3"], n, self.inputs, self.U, self.aux, None, self.Ubar, self._red_l3, self.red_values, self._red_p3)
 
-    def set_couplings(self, items: Sequence[dict], pv: L.EpilogueDesc, p3: L.EpilogueDesc, matrices: Sequence[torch.Tensor]) -> None:
+    def set_couplings(self, items: Sequence, pv: L.EpilogueDesc, p3: L.EpilogueDesc, matrices: Sequence[torch.Tensor]) -> None:
         """Batch-coupled residuals lhs[:R] - M v (graph.couple; ppsci/equation/ide/volterra.py:66-77): `pv` evaluates every v into
         a row of `_cv`, `p3` is the residual program + one LINEAR term per coupling on v with the per-point weight column vbar.
+        `items`: the graph.Coupling records (residual row, aux columns, factor).
         A matrix is a dense [R, N] tensor or a dict of device CSR arrays of M and M^T (compile._csr_to_dev)."""
         f32 = dict(dtype=torch.float32, device=self.U.device)
         assert self.resid is not None
@@ -176,30 +178,30 @@ class FusedConstraint:
         hp.epilogue(cp["pv"], n, self.inputs, self.U, self.aux, self._cv, None, self._cl1)
         for j, (it, M) in enumerate(zip(cp["items"], cp["M"])):
             if isinstance(M, dict):
-                hp.csr_matvec(**M["M"], x=self._cv[j], y=self.aux[it["rhs_aux"]], alpha=it["factor"])
+                hp.csr_matvec(**M["M"], x=self._cv[j], y=self.aux[it.rhs_aux], alpha=it.factor)
             else:
-                hp.dense_matvec(M, self._cv[j], self.aux[it["rhs_aux"]], it["factor"], False)
+                hp.dense_matvec(M, self._cv[j], self.aux[it.rhs_aux], it.factor, False)
         hp.epilogue(self.edesc, n, self.inputs, self.U, self.aux, self.resid, self.Ubar if train else None, self.loss_partials)
         hp.reduce_rows(self.loss_partials, self.loss_rows, max(1, self.edesc.n_res), self.loss_terms, False)
         if not train:
             return
         for it, M in zip(cp["items"], cp["M"]):
-            scale = float(self.edesc.res[it["res_row"]].scale)
+            scale = float(self.edesc.res[it.res_row].scale)
             if isinstance(M, dict):  # vbar = -c M^T (2 scale w d): the CSR product of M^T, w as the scale of its columns
-                hp.csr_matvec(**M["MT"], x=self.resid[it["res_row"]], y=self.aux[it["vbar_aux"]],
-                              alpha=-2.0 * scale * it["factor"], xscale=self.aux[it["weight_aux"]])
+                hp.csr_matvec(**M["MT"], x=self.resid[it.res_row], y=self.aux[it.vbar_aux],
+                              alpha=-2.0 * scale * it.factor, xscale=self.aux[it.weight_aux])
             else:
-                hp.dense_matvec(M, self.resid[it["res_row"]], self.aux[it["vbar_aux"]], -2.0 * scale * it["factor"], True,
-                                rowscale=self.aux[it["weight_aux"]])
+                hp.dense_matvec(M, self.resid[it.res_row], self.aux[it.vbar_aux], -2.0 * scale * it.factor, True,
+                                rowscale=self.aux[it.weight_aux])
         hp.epilogue(cp["p3"], n, self.inputs, self.U, self.aux, None, self.Ubar, self._cl3)
 
-    def set_causal(self, rows: Sequence[tuple], n_chunks: int, tol: float) -> None:
-        """CausalMSELoss (mse.py:109-189): rows = (residual row, label aux, weight aux, area aux, factor aux)."""
+    def set_causal(self, rows: Sequence, n_chunks: int, tol: float) -> None:
+        """CausalMSELoss (mse.py:109-189): rows = graph.CausalRow (residual row, label / weight / area / factor aux)."""
         self.causal, self.n_chunks, self.tol = list(rows), n_chunks, tol
         self.chunk_scratch = torch.zeros((len(self.causal), n_chunks), dtype=torch.float32, device=self.U.device)
 
-    def set_periodic(self, rows: Sequence[tuple]) -> None:
-        """Periodic*Loss (loss/periodic.py): rows = (residual row, label aux); batch = [points ; periodic images]."""
+    def set_periodic(self, rows: Sequence) -> None:
+        """Periodic*Loss (loss/periodic.py): rows = graph.PeriodicRow (residual row, label aux); batch = [points ; images]."""
         self.periodic = list(rows)
 
     def forward(self, params: torch.Tensor, train: bool) -> None:
@@ -222,9 +224,9 @@ class FusedConstraint:
             hp.epilogue(self.edesc, self.n, self.inputs, self.U, self.aux, self.resid, None, self.loss_partials,
                         *self._eq_args(False))
             ax = lambda i: self.aux[i] if i >= 0 else None  # noqa: E731
-            for j, (row, lab, w, ar, cw) in enumerate(self.causal):
-                hp.causal_weights(self.n_chunks, self.tol, self.resid[row], ax(lab), ax(w), ax(ar),
-                                  self.chunk_scratch[j], self.aux[cw])
+            for j, c in enumerate(self.causal):
+                hp.causal_weights(self.n_chunks, self.tol, self.resid[c.row], ax(c.label_aux), ax(c.weight_aux), ax(c.area_aux),
+                                  self.chunk_scratch[j], self.aux[c.factor_aux])
         periodic = getattr(self, "periodic", None)
         if periodic:
             # first pass: values only; every point's label becomes its partner's value (a constant for the reverse
@@ -232,9 +234,9 @@ class FusedConstraint:
             hp.epilogue(self.edesc, self.n, self.inputs, self.U, self.aux, self.resid, None, self.loss_partials,
                         *self._eq_args(False))
             h = self.n // 2
-            for row, lab in periodic:
-                self.aux[lab][:h].copy_(self.resid[row][h:])
-                self.aux[lab][h:].copy_(self.resid[row][:h])
+            for p in periodic:
+                self.aux[p.label_aux][:h].copy_(self.resid[p.row][h:])
+                self.aux[p.label_aux][h:].copy_(self.resid[p.row][:h])
         if not periodic and self.edesc.n_res >= 1 and _EPI_LOSSES:
             # the loss terms come out of the epilogue launch itself (the workgroup that finishes last sums the rows)
             hp.epilogue(self.edesc, self.n, self.inputs, self.U, self.aux, self.resid, self.Ubar if train else None,
@@ -245,8 +247,8 @@ class FusedConstraint:
 
         hp.reduce_rows(self.loss_partials, self.loss_rows, max(1, self.edesc.n_res), self.loss_terms, False)
         if periodic:
-            for row, _ in periodic:
-                self.loss_terms[row:row + 1].mul_(0.5)
+            for p in periodic:
+                self.loss_terms[p.row:p.row + 1].mul_(0.5)
 
     def _eq_args(self, train: bool):
         st = getattr(self, "eq_store", None)

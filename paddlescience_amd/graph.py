@@ -16,9 +16,10 @@ computes numerically (ad.py:73-75).
 from __future__ import annotations
 
 import contextlib
-import itertools
-import zlib
+import dataclasses
 import math
+import weakref
+import zlib
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -40,12 +41,14 @@ _BINARY_OPS = {"add": L.OP_ADD, "sub": L.OP_SUB, "mul": L.OP_MUL, "div": L.OP_DI
 
 
 class Sym:
-    """A per-point scalar field ([N, 1] in the reference).  Immutable; hash-consed by structure."""
+    """A per-point scalar field ([N, 1] in the reference).  Immutable; hash-consed by structure: the table holds its nodes
+    weakly (a node keeps its arguments and its model alive, so the ids in a key cannot be recycled while its entry exists),
+    and a trace that is dropped takes its nodes -- and the models they hold -- with it."""
 
-    __slots__ = ("kind", "name", "value", "model", "comp", "dirs", "op", "args", "_key")
-    _cache: Dict[tuple, "Sym"] = {}
+    __slots__ = ("kind", "name", "value", "model", "comp", "dirs", "op", "args", "matrix", "_key", "__weakref__")
+    _cache: "weakref.WeakValueDictionary[tuple, Sym]" = weakref.WeakValueDictionary()
 
-    def __new__(cls, kind, name=None, value=None, model=None, comp=None, dirs=(), op=None, args=()):
+    def __new__(cls, kind, name=None, value=None, model=None, comp=None, dirs=(), op=None, args=(), matrix=None):
         key = (kind, name, None if value is None else float(np.float32(value)), id(model) if model is not None else None,
                comp, tuple(dirs), op, tuple(id(a) for a in args))
         hit = cls._cache.get(key)
@@ -55,6 +58,7 @@ class Sym:
         self.kind, self.name, self.model, self.comp = kind, name, model, comp
         self.value = None if value is None else float(np.float32(value))  # ConstantNode: fp32 (symbolic.py:448-454)
         self.dirs, self.op, self.args = tuple(dirs), op, tuple(args)
+        self.matrix = matrix  # `couple` nodes: the constant matrix (in the key by its crc -- the name -- and its shape)
         self._key = key
         cls._cache[key] = self
         return self
@@ -388,11 +392,9 @@ def concrete_values(s: "Sym", what: str = "value") -> np.ndarray:
 # lower() turns it into a per-point program around two small matrix-vector launches (engine.FusedConstraint._forward_couplings).
 # M is dense (Volterra: a few hundred entries) or a CsrMatrix (the fractional Laplacian, ppsci/equation/fpde/
 # fractional_poisson.py:57-82: ~690 nonzeros per row of 100 k to 1.4 M columns), and may carry a scalar factor c (the residual is
-# lhs - c M v, the factor applied by the kernel's alpha, not rounded into the entries).  The matrices wait here between the
-# trace and the upload of the compiled constraint, which takes them out (CompiledConstraint: `take_coupling`).
+# lhs - c M v, the factor applied by the kernel's alpha, not rounded into the entries).  The matrix travels on the `couple`
+# node and from there into the Coupling record of lower(); CompiledConstraint uploads it and drops the host copy.
 COUPLE_RHS_PREFIX, COUPLE_VBAR_PREFIX = "__couple_rhs__", "__couple_vbar__"
-_COUPLE_MATS: Dict[str, object] = {}
-_COUPLE_SEQ = itertools.count()
 
 
 class CsrMatrix:
@@ -451,15 +453,8 @@ def couple(lhs, matrix, v, factor: Optional[float] = None) -> "Sym":
         if M.ndim != 2:
             raise ValueError(f"couple(): a [rows, batch] matrix is needed, got shape {M.shape}")
         crc = zlib.crc32(M.tobytes())
-    name = f"couple{next(_COUPLE_SEQ)}_{crc:08x}"
-    _COUPLE_MATS[name] = M
-    return Sym("couple", name=name, value=None if factor is None else float(factor), comp=(int(M.shape[0]), int(M.shape[1])),
-               args=(_lift(lhs), _lift(v)))
-
-
-def take_coupling(name: str):
-    """The matrix of coupling `name`, removed from the registry (the caller uploads it once)."""
-    return _COUPLE_MATS.pop(name)
+    return Sym("couple", name=f"couple_{crc:08x}", value=None if factor is None else float(factor),
+               comp=(int(M.shape[0]), int(M.shape[1])), args=(_lift(lhs), _lift(v)), matrix=M)
 
 
 def _lift(v) -> Sym:
@@ -561,9 +556,7 @@ def directional(e: Sym, d, order: int) -> Sym:
 def diff(e: Sym, var: str) -> Sym:
     """d e / d var, symbolically (what jacobian() obtains numerically in the reference)."""
     k = e.kind
-    if k == "in":
-        return Sym.const(1.0 if e.name == var else 0.0)
-    if k == "aux":  # a dataset column that is not a network input (raw variable of an input transform, nu, sdf, ...)
+    if k in ("in", "aux"):  # (aux: a dataset column that is not a network input -- raw variable of an input transform, nu, sdf, ...)
         return Sym.const(1.0 if e.name == var else 0.0)
     if k in ("const", "param"):
         return Sym.const(0.0)
@@ -614,45 +607,33 @@ def diff(e: Sym, var: str) -> Sym:
         den = a[0] * a[0] + a[1] * a[1]
         return (a[1] * diff(a[0], var) - a[0] * diff(a[1], var)) / den
     d = diff(a[0], var)
-    if is_const(d, 0.0):
-        return d
-    if op == "asin":
-        return d / apply("sqrt", 1.0 - a[0] * a[0])
-    if op == "acos":
-        return -(d / apply("sqrt", 1.0 - a[0] * a[0]))
-    if op == "atan":
-        return d / (1.0 + a[0] * a[0])
-    if op == "asinh":
-        return d / apply("sqrt", a[0] * a[0] + 1.0)
-    if op == "acosh":
-        return d / apply("sqrt", a[0] * a[0] - 1.0)
-    if op == "atanh":
-        return d / (1.0 - a[0] * a[0])
-    if op == "erf":
-        return apply("exp", -(a[0] * a[0])) * (2.0 / math.sqrt(math.pi)) * d
-    if op == "sin":
-        return apply("cos", a[0]) * d
-    if op == "cos":
-        return -(apply("sin", a[0]) * d)
-    if op == "tanh":
-        return (1.0 - e * e) * d
-    if op == "exp":
-        return e * d
-    if op == "log":
-        return d / a[0]
-    if op == "sqrt":
-        return d / (2.0 * e)
-    if op == "abs":
-        return apply("sign", a[0]) * d
-    if op == "sinh":
-        return apply("cosh", a[0]) * d
-    if op == "cosh":
-        return apply("sinh", a[0]) * d
-    if op == "tan":
-        return (1.0 + e * e) * d
-    if op in ("sign", "heaviside", "ceil", "floor"):
+    if is_const(d, 0.0) or op in ("sign", "heaviside", "ceil", "floor"):
         return Sym.const(0.0)
-    raise NotImplementedError(f"derivative of {op!r}")
+    if op not in _UNARY_DIFF:
+        raise NotImplementedError(f"derivative of {op!r}")
+    return _UNARY_DIFF[op](e, a[0], d)
+
+
+# d f(a) / d var of the elementwise functions, from e = f(a), a and d = d a / d var
+_UNARY_DIFF = {
+    "asin": lambda e, a, d: d / apply("sqrt", 1.0 - a * a),
+    "acos": lambda e, a, d: -(d / apply("sqrt", 1.0 - a * a)),
+    "atan": lambda e, a, d: d / (1.0 + a * a),
+    "asinh": lambda e, a, d: d / apply("sqrt", a * a + 1.0),
+    "acosh": lambda e, a, d: d / apply("sqrt", a * a - 1.0),
+    "atanh": lambda e, a, d: d / (1.0 - a * a),
+    "erf": lambda e, a, d: apply("exp", -(a * a)) * (2.0 / math.sqrt(math.pi)) * d,
+    "sin": lambda e, a, d: apply("cos", a) * d,
+    "cos": lambda e, a, d: -(apply("sin", a) * d),
+    "tanh": lambda e, a, d: (1.0 - e * e) * d,
+    "exp": lambda e, a, d: e * d,
+    "log": lambda e, a, d: d / a,
+    "sqrt": lambda e, a, d: d / (2.0 * e),
+    "abs": lambda e, a, d: apply("sign", a) * d,
+    "sinh": lambda e, a, d: apply("cosh", a) * d,
+    "cosh": lambda e, a, d: apply("sinh", a) * d,
+    "tan": lambda e, a, d: (1.0 + e * e) * d,
+}
 
 
 # ----------------------------------------------------------------------------- lowering
@@ -679,20 +660,90 @@ _INSTANTIATED = [(0, 0, 0, 0), (1, 1, 0, 0), (2, 0, 0, 0), (2, 1, 0, 0), (2, 2, 
                  (1, 1, 1, 0), (1, 1, 1, 1), (2, 2, 2, 2), (4, 4, 4, 4)]
 
 
+@dataclasses.dataclass(frozen=True)
+class LossTerm:
+    """One loss term, as lower() takes it: the output `key` against the aux columns named here (compile.loss_terms)."""
+    key: str
+    label: Optional[str] = None
+    weight: Optional[str] = None
+    area: Optional[str] = None
+    scale: float = 1.0
+    kind: int = 0  # hotpath.LOSS_*
+    causal: Optional[str] = None  # CausalMSELoss: the aux column that carries the causal factor
+    periodic: bool = False
+
+
+@dataclasses.dataclass(frozen=True)
+class NetSlot:
+    """One network of the constraint and its block of rows of U."""
+    model: object
+    spec: hp.StreamSpec  # in ITS input order
+    row0: int  # first row of U
+    inputs: Optional[List[int]]  # indices of its inputs among the constraint's (None under an input transform)
+    pre: Optional[List[tuple]] = None  # stream programs of an input transform: (Program, first feature row, rows)
+
+
+@dataclasses.dataclass(frozen=True)
+class CausalRow:
+    """CausalMSELoss: a residual row and its label / weight / area / causal-factor aux columns (-1: none)."""
+    row: int
+    label_aux: int
+    weight_aux: int
+    area_aux: int
+    factor_aux: int
+
+
+@dataclasses.dataclass(frozen=True)
+class PeriodicRow:
+    """Periodic*Loss: the label column of this residual row receives the partner half's values."""
+    row: int
+    label_aux: int
+
+
+@dataclasses.dataclass(frozen=True)
+class Coupling:
+    """One batch coupling lhs[:rows] - factor * (M v): its residual row and aux columns, and M itself until it is uploaded."""
+    name: str
+    rows: int
+    cols: int
+    res_row: int
+    weight_aux: int
+    rhs_aux: int
+    vbar_aux: int
+    factor: float
+    matrix: object = None
+
+
+@dataclasses.dataclass(frozen=True)
+class CouplingPlan:
+    items: Tuple[Coupling, ...]
+    pv: hp.Program  # value pass: v of every coupling into a row of a [C, N] buffer
+    p3: hp.Program  # adjoint pass: the residual program + one LINEAR term per coupling on v
+
+
+@dataclasses.dataclass(frozen=True)
+class ReductionPlan:
+    k: int
+    p1: hp.Program  # pass 1: the summands alone, one LINEAR term each
+    p3: hp.Program  # pass 3: the residual program + one LINEAR term per summand, seeded with dL/dR_k
+
+
+@dataclasses.dataclass
 class Lowered:
     """Result of lowering: everything engine.FusedConstraint needs except the device arrays."""
-
-    def __init__(self, model, streams: hp.StreamSpec, program: hp.Program, input_names: List[str],
-                 aux_names: List[str], loss_keys: List[str], value_index: Dict[str, int]):
-        self.model, self.streams, self.program = model, streams, program
-        self.input_names, self.aux_names, self.loss_keys = input_names, aux_names, loss_keys
-        self.value_index = value_index  # output name -> program value index
-        self.causal: List[tuple] = []
-        self.periodic: List[tuple] = []
-        self.param_slots: List[int] = []  # slots of the learnable equation parameters the program reads
-        self.couplings: Optional[dict] = None  # batch couplings: {"items": [...], "pv": value program, "p3": adjoint program}
-        self.reductions: Optional[dict] = None  # batch reductions: {"k": count, "p1": summand program, "p3": adjoint program}
-        self.nets: List[tuple] = []  # (model, StreamSpec, first U row, input indices) per network of the constraint
+    model: object
+    streams: Optional[hp.StreamSpec]
+    program: hp.Program
+    input_names: List[str]
+    aux_names: List[str]
+    loss_keys: List[str]
+    value_index: Dict[str, int]  # output name -> program value index
+    nets: List[NetSlot]
+    causal: List[CausalRow]
+    periodic: List[PeriodicRow]
+    param_slots: List[int]  # slots of the learnable equation parameters the program reads
+    couplings: Optional[CouplingPlan] = None
+    reductions: Optional[ReductionPlan] = None
 
 
 def _check_separable(nodes, losses, jet) -> None:
@@ -711,28 +762,17 @@ def _check_separable(nodes, losses, jet) -> None:
         if n.kind == "net" and n.model is not jet.model:
             raise NotImplementedError(f"a second network in a {what} residual")
     for ls in losses:
-        if ls.get("periodic"):
+        if ls.periodic:
             raise NotImplementedError(f"periodic loss on a {what} grid: its pairs are halves of a batch column")
-        if ls.get("causal"):
+        if ls.causal:
             raise NotImplementedError(f"causal loss on a {what} grid: its windows are chunks of a batch column")
-        if ls.get("area"):
+        if ls.area:
             raise NotImplementedError(f"area column on a {what} grid")
 
 
-def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequence[str] = (),
-          n_global: Optional[int] = None, jet=None) -> Lowered:
-    """outputs: name -> traced expression.  losses: dicts with keys
-         key (output name), label (aux name or None), weight (aux name or None), area (aux name or None), scale.
-       Residual row k of the epilogue corresponds to losses[k]; `extra_outputs` are appended as
-       scale-0 residual rows so that eval / predict can read their values.
-       jet: the stream choice of a separable net (arch.spinn.JetTable) instead of the Taylor kernels' direction set: U row q is
-       the q-th distinct per-axis order triple the program reads, in order of first use; the program is emitted as for any
-       other model."""
-    roots = list(outputs.values())
-    nodes = _walk(roots)
-    if jet is not None:
-        _check_separable(nodes, losses, jet)
-    # batch reductions (Sym.mean / Sym.sum): reduction k is read from parameter slot k by the residual program
+def _validate(nodes, roots, n_global) -> Tuple[List[Sym], List[Sym], list]:
+    """The batch reductions (Sym.mean / Sym.sum), the batch couplings (couple) and the networks (ModelList members, in
+    order of appearance) among `nodes`, checked."""
     reduces = [n for n in nodes if n.kind == "reduce"]
     if reduces:
         if any(n.kind == "param" for n in nodes):
@@ -744,59 +784,75 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
                                       "one level is lowered")
         if any(r.op == "mean" for r in reduces) and not n_global:
             raise NotImplementedError("mean() over the batch needs the global batch size")
-    red_slot = {id(r): k for k, r in enumerate(reduces)}
     couples = [n for n in nodes if n.kind == "couple"]
     if couples:
         if reduces:
             raise NotImplementedError("batch couplings together with batch reductions")
         if any(id(c) not in {id(r) for r in roots} for c in couples) or any(a.kind == "couple" for n in nodes for a in n.args):
             raise NotImplementedError("a batch-coupled residual must be the whole output expression")
-    models = {id(n.model): n.model for n in nodes if n.kind == "net"}  # ModelList members: in order of appearance
-    model_list = list(models.values())
-    model = model_list[0] if model_list else None
+    model_list = list({id(n.model): n.model for n in nodes if n.kind == "net"}.values())
     for mm in model_list:  # operator nets: a multi-column branch key is no per-point variable of the residual program
         cols = getattr(mm, "branch_cols", None) or {}
         for n in nodes:
             if n.kind in ("in", "aux") and cols.get(n.name, 1) != 1:
                 raise NotImplementedError(f"expression reads the {cols[n.name]}-column branch key {n.name!r} of "
                                           f"{type(mm).__name__}: only one-column keys are per-point values")
+    return reduces, couples, model_list
 
-    # ---- derivative set -> stream specification
-    # order[d] = highest pure derivative order needed along direction d (a variable, (a, b) = a + b, (a, b, -1) = a - b)
+
+def _pure_streams(dirs) -> Optional[Tuple[list, bool]]:
+    """The pure directional streams (all of order len(dirs)) the derivative `dirs` of a network output is assembled from, in
+    the order the program loads them -- a direction is a variable, (a, b) for a + b or (a, b, -1.0) for a - b -- or None
+    where the kernels carry no such set.  Read by the stream plan (which directions, to which order) and by
+    _Emitter._net (the arithmetic on the loaded streams):
+        u_ab   = (D2_{a+b} - D2_a - D2_b) / 2
+        u_aab  = (D3_{a+b} - D3_{a-b} - 2 D3_b) / 6        (D3_{a+-b} = u_aaa +- 3 u_aab + 3 u_abb +- u_bbb)
+        u_aabb = (D4_{a+b} + D4_{a-b} - 2 D4_a - 2 D4_b) / 12
+    The flag is for u_aab: the difference stream is kept along lo - hi of the sorted pair (D3 along b - a is minus D3 along
+    a - b: one stream serves u_aab and u_abb), and the flag says that this IS a - b."""
+    vs, k = sorted(set(dirs)), len(dirs)
+    if len(vs) == 1:
+        return [vs[0]], True
+    if k == 2:  # (a + b and b + a are ONE direction: one key)
+        return [(vs[0], vs[1]), vs[0], vs[1]], True
+    if k == 4 and len(vs) == 2 and dirs.count(vs[0]) == 2:
+        return [(vs[0], vs[1]), (vs[0], vs[1], -1.0), vs[0], vs[1]], True
+    if k == 3 and len(vs) == 2:  # (the shear forces of examples/biharmonic2d/biharmonic2d.py:325-336: d/dx (u_xx + u_yy))
+        a, b = (vs[0], vs[1]) if dirs.count(vs[0]) == 2 else (vs[1], vs[0])
+        return [(vs[0], vs[1]), (vs[0], vs[1], -1.0), b], a == vs[0]
+    return None
+
+
+@dataclasses.dataclass(frozen=True)
+class _StreamPlan:
+    """The derivative streams of one lowering: the constraint's input variables, the directions in stream order (higher
+    orders first), their vectors padded to the instantiated (n1, n2, n3, n4) `counts`, and the StreamSpec (None: a jet)."""
+    in_keys: List[str]
+    dir_names: List[object]
+    dirs_vec: List[List[float]]
+    counts: Tuple[int, int, int, int]
+    streams: Optional[hp.StreamSpec]
+
+    @property
+    def S(self) -> int:
+        return self.streams.S if self.streams is not None else 1
+
+
+def _plan_streams(nodes, model_list, jet) -> _StreamPlan:
+    # order[d] = highest pure derivative order needed along direction d
     order: Dict[object, int] = {}
-    mixed, mixed4 = set(), set()
-
-    def need(d, k):
-        order[d] = max(order.get(d, 0), k)
-
     for n in nodes:
         if n.kind != "net" or not n.dirs or jet is not None:
             continue
-        vs = sorted(set(n.dirs))
-        k = len(n.dirs)
-        if len(vs) == 1:
-            need(vs[0], k)
-        elif k == 2:
-            a, b = sorted(n.dirs)  # (a + b and b + a are ONE direction: one key)
-            mixed.add((a, b))
-            need(a, 2), need(b, 2), need((a, b), 2)
-        elif k == 4 and len(vs) == 2 and n.dirs.count(vs[0]) == 2:
-            a, b = vs  # u_aabb = (D4_{a+b} + D4_{a-b} - 2 D4_a - 2 D4_b) / 12
-            mixed4.add((a, b))
-            need(a, 4), need(b, 4), need((a, b), 4), need((a, b, -1.0), 4)
-        elif k == 3 and len(vs) == 2:
-            # u_aab (a twice, b once) = (D3_{a+b} - D3_{a-b} - 2 D3_b) / 6: D3_{a+-b} = u_aaa +- 3 u_aab + 3 u_abb +- u_bbb
-            # (the shear forces of examples/biharmonic2d/biharmonic2d.py:325-336: d/dx (u_xx + u_yy))
-            a, b = (vs[0], vs[1]) if n.dirs.count(vs[0]) == 2 else (vs[1], vs[0])
-            lo, hi = sorted((a, b))  # (D3 along b - a is minus D3 along a - b: one stream serves u_aab and u_abb)
-            need(b, 3), need((lo, hi), 3), need((lo, hi, -1.0), 3)
-        else:
+        pure = _pure_streams(n.dirs)
+        if pure is None:
             raise NotImplementedError(
                 f"mixed derivative {n!r}: beyond pure derivatives the fused HIP kernels carry u_ab, u_aab and u_aabb")
+        for d in pure[0]:
+            order[d] = max(order.get(d, 0), len(n.dirs))
     in_keys: List[str] = []  # union of the members' inputs: the constraint's input arrays
     for mm in model_list:
         in_keys += [k for k in net_raw_vars(mm) if k not in in_keys]
-
     if jet is not None:
         in_keys = list(jet.model.input_keys)
 
@@ -804,10 +860,7 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
         return (0, in_keys.index(d)) if isinstance(d, str) else (1, repr(d))
 
     dir_names: List[object] = sorted(order, key=lambda d: (-order[d], rank(d)))  # higher orders first: prefix property
-    n1 = len(dir_names)
-    n2 = sum(1 for d in dir_names if order[d] >= 2)
-    n3 = sum(1 for d in dir_names if order[d] >= 3)
-    n4 = sum(1 for d in dir_names if order[d] >= 4)
+    n1, n2, n3, n4 = (sum(1 for d in dir_names if order[d] >= k) for k in (1, 2, 3, 4))
     choice = None
     for c in _INSTANTIATED:
         if c[0] >= n1 and c[1] >= n2 and c[2] >= n3 and c[3] >= n4 and (choice is None or (c[2:], c[:2]) < (choice[2:], choice[:2])):
@@ -824,27 +877,25 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
         else:
             v[in_keys.index(d)] = 1.0
         dirs_vec.append(v)
-    n1p, n2p, n3p, n4p = choice
-    while len(dirs_vec) < n1p:  # padding directions are zero vectors: their streams vanish identically
+    while len(dirs_vec) < choice[0]:  # padding directions are zero vectors: their streams vanish identically
         dirs_vec.append([0.0] * len(in_keys))
-    streams = hp.StreamSpec(dirs_vec, n2p, n3p, n4p) if jet is None else None
-    S = streams.S if jet is None else 1
-    dir_index = {d: i for i, d in enumerate(dir_names)}
+    streams = hp.StreamSpec(dirs_vec, *choice[1:]) if jet is None else None
+    return _StreamPlan(in_keys, dir_names, dirs_vec, choice, streams)
 
-    # every member carries the same stream set; its direction vectors are expressed in ITS input order (a
-    # variable a member does not take contributes nothing: its derivative along it is zero), and its streams
-    # are a block of rows of the constraint's U / Ubar arrays
-    nets = []  # (model, StreamSpec, first U row, indices of its inputs in in_keys)
-    row0: Dict[int, int] = {}
-    rows = 0
-    pre_nets: Dict[int, list] = {}  # id(model) -> per-feature stream expressions (input transform)
-    for mm in ([] if jet is not None else model_list):
+
+def _net_slots(model_list, plan: _StreamPlan) -> Tuple[List[NetSlot], Dict[int, list]]:
+    """Every member carries the same stream set; its direction vectors are expressed in ITS input order (a variable a
+    member does not take contributes nothing: its derivative along it is zero), and its streams are a block of rows of the
+    constraint's U / Ubar arrays.  Also: id(model) -> per-feature stream expressions of a registered input transform."""
+    slots, features, rows = [], {}, 0
+    n1p, n2p, n3p, n4p = plan.counts
+    padded = list(plan.dir_names) + [None] * (n1p - len(plan.dir_names))
+    for mm in model_list:
         feats = getattr(mm, "_traced_features", None)
         if feats:
             # a registered input transform: the network's inputs are functions phi_k of the raw variables; the
             # kernels take phi_k and its derivative streams along the directions as [S, N] blocks (EMBED_STREAMS)
             idx = None
-            padded = list(dir_names) + [None] * (n1p - len(dir_names))
             blocks = []
             for k in mm.input_keys:
                 phi = feats[k]
@@ -852,211 +903,211 @@ def lower(outputs: Dict[str, Sym], losses: Sequence[dict], extra_outputs: Sequen
                 for kk, npk in ((2, n2p), (3, n3p), (4, n4p)):
                     rows_k += [Sym.const(0.0) if d is None else directional(phi, d, kk) for d in padded[:npk]]
                 blocks.append(rows_k)
-            pre_nets[id(mm)] = blocks
+            features[id(mm)] = blocks
             spec = hp.StreamSpec([[0.0] * len(mm.input_keys) for _ in range(n1p)], n2p, n3p, n4p)
         else:
-            idx = [in_keys.index(k) for k in net_raw_vars(mm)]
-            spec = hp.StreamSpec([[v[j] for j in idx] for v in dirs_vec], n2p, n3p, n4p)
-        nets.append((mm, spec, rows, idx))
-        row0[id(mm)] = rows
-        rows += len(mm.output_keys) * S
-    prog = hp.Program(rows, len(in_keys))
-    # inputs that are not network inputs (e.g. parameters of a boundary function) are shipped as aux arrays
-    input_names = list(in_keys)
-    aux_names: List[str] = []
+            idx = [plan.in_keys.index(k) for k in net_raw_vars(mm)]
+            spec = hp.StreamSpec([[v[j] for j in idx] for v in plan.dirs_vec], n2p, n3p, n4p)
+        slots.append(NetSlot(mm, spec, rows, idx))
+        rows += len(mm.output_keys) * plan.S
+    return slots, features
 
-    def aux_index(name: str) -> int:
-        if name not in aux_names:
-            aux_names.append(name)
-        return aux_names.index(name)
 
-    val: Dict[int, int] = {}
-    param_slots = set()
+class _Emitter:
+    """Writes traced nodes into epilogue programs.  One per lowering: its programs share the aux-column table (inputs that
+    are not network inputs, e.g. parameters of a boundary function, are shipped as aux arrays) and the parameter slots."""
 
-    def emit_pointwise(pg: hp.Program, pnodes, pval: Dict[int, int]) -> None:
-        """Inputs, aux arrays, constants and operators only (the stream programs of an input transform)."""
-        for n in pnodes:
-            if n.kind == "in":
-                pval[id(n)] = pg.ld_in(input_names.index(n.name)) if n.name in input_names else pg.ld_aux(aux_index(n.name))
-            elif n.kind == "aux":
-                pval[id(n)] = pg.ld_in(input_names.index(n.name)) if n.name in input_names else pg.ld_aux(aux_index(n.name))
-            elif n.kind == "const":
-                pval[id(n)] = pg.const(n.value)
-            elif n.kind in ("net", "param"):
-                raise NotImplementedError("an input transform may only use the data-dict variables")
-            elif n.op in _BINARY_OPS:
-                pval[id(n)] = pg.op(_BINARY_OPS[n.op], pval[id(n.args[0])], pval[id(n.args[1])])
-            else:
-                pval[id(n)] = pg.op(_UNARY_OPS[n.op], pval[id(n.args[0])])
+    def __init__(self, plan: _StreamPlan, slots: Sequence[NetSlot], reduces, couples, jet):
+        self.plan, self.jet = plan, jet
+        self.row0 = {id(s.model): s.row0 for s in slots}
+        self.red_slot = {id(r): k for k, r in enumerate(reduces)}  # reduction k is read from parameter slot k
+        self.couple_name = {id(c): f"couple{k}" for k, c in enumerate(couples)}
+        self.dir_index = {d: i for i, d in enumerate(plan.dir_names)}
+        self.input_names: List[str] = list(plan.in_keys)
+        self.aux_names: List[str] = []
+        self.param_slots = set()
 
-    def emit(prog: hp.Program, nodes, val: Dict[int, int]) -> None:
-        """The residual program of `nodes` (in dependency order) into `prog`; val: node id -> value index."""
+    def aux_index(self, name: str) -> int:
+        if name not in self.aux_names:
+            self.aux_names.append(name)
+        return self.aux_names.index(name)
+
+    def emit(self, prog: hp.Program, nodes, val: Dict[int, int], pointwise: bool = False) -> None:
+        """`nodes` (in dependency order) into `prog`; val: node id -> value index.  pointwise: inputs, aux arrays, constants
+        and operators only (the stream programs of an input transform)."""
         for n in nodes:
-            if n.kind == "in":
-                if n.name in input_names:
-                    val[id(n)] = prog.ld_in(input_names.index(n.name))
-                else:
-                    val[id(n)] = prog.ld_aux(aux_index(n.name))
-            elif n.kind == "aux":
-                val[id(n)] = prog.ld_in(input_names.index(n.name)) if n.name in input_names else prog.ld_aux(aux_index(n.name))
-            elif n.kind == "param":
-                val[id(n)] = prog.ld_param(n.comp)
-                param_slots.add(n.comp)
-            elif n.kind == "reduce":
-                val[id(n)] = prog.ld_param(red_slot[id(n)])
-            elif n.kind == "couple":  # lhs - (M v): the product is an aux column written between two launches
-                val[id(n)] = prog.op(L.OP_SUB, val[id(n.args[0])], prog.ld_aux(aux_index(COUPLE_RHS_PREFIX + n.name)))
+            if n.kind in ("in", "aux"):
+                v = prog.ld_in(self.input_names.index(n.name)) if n.name in self.input_names else prog.ld_aux(self.aux_index(n.name))
             elif n.kind == "const":
-                val[id(n)] = prog.const(n.value)
-            elif n.kind == "net" and jet is not None:
-                val[id(n)] = prog.ld_u(jet.row(n))
+                v = prog.const(n.value)
+            elif pointwise and n.kind in ("net", "param"):
+                raise NotImplementedError("an input transform may only use the data-dict variables")
+            elif n.kind == "param":
+                v = prog.ld_param(n.comp)
+                self.param_slots.add(n.comp)
+            elif n.kind == "reduce":
+                v = prog.ld_param(self.red_slot[id(n)])
+            elif n.kind == "couple":  # lhs - (M v): the product is an aux column written between two launches
+                v = prog.op(L.OP_SUB, val[id(n.args[0])], prog.ld_aux(self.aux_index(COUPLE_RHS_PREFIX + self.couple_name[id(n)])))
             elif n.kind == "net":
-                c = n.comp + row0[id(n.model)] // S  # rows of a member start at a multiple of S
-                if len(n.dirs) == 0:
-                    val[id(n)] = prog.ld_u(c * S)
-                elif len(n.dirs) == 1:
-                    val[id(n)] = prog.ld_u(c * S + 1 + dir_index[n.dirs[0]])
-                else:
-                    base = {2: 1 + n1p, 3: 1 + n1p + n2p, 4: 1 + n1p + n2p + n3p}[len(n.dirs)]
-                    vs = sorted(set(n.dirs))
-                    if len(vs) == 1:
-                        val[id(n)] = prog.ld_u(c * S + base + dir_index[vs[0]])
-                    elif len(n.dirs) == 2:  # polarisation: u_ab = (D2_{a+b} - D2_a - D2_b) / 2
-                        a, b = sorted(n.dirs)
-                        sab = prog.ld_u(c * S + base + dir_index[(a, b)])
-                        sa = prog.ld_u(c * S + base + dir_index[a])
-                        sb = prog.ld_u(c * S + base + dir_index[b])
-                        t = prog.op(L.OP_SUB, prog.op(L.OP_SUB, sab, sa), sb)
-                        val[id(n)] = prog.op(L.OP_MUL, prog.const(0.5), t)
-                    elif len(n.dirs) == 3:  # u_aab = (D3_{a+b} - D3_{a-b} - 2 D3_b) / 6
-                        a, b = (vs[0], vs[1]) if n.dirs.count(vs[0]) == 2 else (vs[1], vs[0])
-                        lo, hi = sorted((a, b))
-                        sp_ = prog.ld_u(c * S + base + dir_index[(lo, hi)])
-                        sm_ = prog.ld_u(c * S + base + dir_index[(lo, hi, -1.0)])  # D3 along lo - hi = +- D3 along a - b
-                        sb = prog.ld_u(c * S + base + dir_index[b])
-                        t = prog.op(L.OP_SUB if a == lo else L.OP_ADD, sp_, sm_)
-                        t = prog.op(L.OP_SUB, t, prog.op(L.OP_MUL, prog.const(2.0), sb))
-                        val[id(n)] = prog.op(L.OP_MUL, prog.const(1.0 / 6.0), t)
-                    else:  # u_aabb = (D4_{a+b} + D4_{a-b} - 2 D4_a - 2 D4_b) / 12
-                        a, b = vs
-                        sp_ = prog.ld_u(c * S + base + dir_index[(a, b)])
-                        sm_ = prog.ld_u(c * S + base + dir_index[(a, b, -1.0)])
-                        sa = prog.ld_u(c * S + base + dir_index[a])
-                        sb = prog.ld_u(c * S + base + dir_index[b])
-                        two = prog.const(2.0)
-                        t = prog.op(L.OP_SUB, prog.op(L.OP_SUB, prog.op(L.OP_ADD, sp_, sm_), prog.op(L.OP_MUL, two, sa)),
-                                    prog.op(L.OP_MUL, two, sb))
-                        val[id(n)] = prog.op(L.OP_MUL, prog.const(1.0 / 12.0), t)
+                v = prog.ld_u(self.jet.row(n)) if self.jet is not None else self._net(prog, n)
+            elif n.op in _BINARY_OPS:
+                v = prog.op(_BINARY_OPS[n.op], val[id(n.args[0])], val[id(n.args[1])])
             else:
-                if n.op in _BINARY_OPS:
-                    val[id(n)] = prog.op(_BINARY_OPS[n.op], val[id(n.args[0])], val[id(n.args[1])])
-                else:
-                    val[id(n)] = prog.op(_UNARY_OPS[n.op], val[id(n.args[0])])
+                v = prog.op(_UNARY_OPS[n.op], val[id(n.args[0])])
+            val[id(n)] = v
+
+    def _net(self, prog: hp.Program, n: Sym) -> int:
+        """A network output or derivative from the streams of its member (rows of a member start at a multiple of S); the
+        identities of the mixed ones are stated at _pure_streams."""
+        S, k = self.plan.S, len(n.dirs)
+        q0 = (n.comp + self.row0[id(n.model)] // S) * S
+        if k == 0:
+            return prog.ld_u(q0)
+        n1p, n2p, n3p, _ = self.plan.counts
+        base = q0 + (1, 1 + n1p, 1 + n1p + n2p, 1 + n1p + n2p + n3p)[k - 1]
+        streams, a_minus_b = _pure_streams(n.dirs)
+        s = [prog.ld_u(base + self.dir_index[d]) for d in streams]
+        if len(s) == 1:
+            return s[0]
+        if k == 2:
+            t = prog.op(L.OP_SUB, prog.op(L.OP_SUB, s[0], s[1]), s[2])
+            return prog.op(L.OP_MUL, prog.const(0.5), t)
+        if k == 3:
+            t = prog.op(L.OP_SUB if a_minus_b else L.OP_ADD, s[0], s[1])
+            t = prog.op(L.OP_SUB, t, prog.op(L.OP_MUL, prog.const(2.0), s[2]))
+            return prog.op(L.OP_MUL, prog.const(1.0 / 6.0), t)
+        two = prog.const(2.0)
+        t = prog.op(L.OP_SUB, prog.op(L.OP_SUB, prog.op(L.OP_ADD, s[0], s[1]), prog.op(L.OP_MUL, two, s[2])),
+                    prog.op(L.OP_MUL, two, s[3]))
+        return prog.op(L.OP_MUL, prog.const(1.0 / 12.0), t)
 
 
-    emit(prog, nodes, val)
-    if jet is not None:
-        prog.n_streams = len(jet.orders)
-
-    loss_keys = []
-    couple_rows: Dict[str, tuple] = {}  # coupling name -> (residual row, weight aux)
-    periodic = []  # (residual row, label aux) -- Periodic*Loss: the label row receives the partner half's values
-    causal = []  # (residual row, label aux, weight aux, area aux, causal-factor aux) -- CausalMSELoss
+def _emit_losses(em: _Emitter, prog: hp.Program, val, outputs, losses, extra_outputs):
+    """Residual row k of the program is losses[k]; `extra_outputs` follow as scale-0 rows.  Returns the row names, the
+    causal and periodic rows and, per coupled output (node id), its (residual row, weight aux)."""
+    loss_keys, causal, periodic, couple_rows = [], [], [], {}
     for ls in losses:
-        key = ls["key"]
-        lab = aux_index(ls["label"]) if ls.get("label") else -1
-        w = aux_index(ls["weight"]) if ls.get("weight") else -1
-        ar = aux_index(ls["area"]) if ls.get("area") else -1
-        if ls.get("causal"):
+        out = outputs[ls.key]
+        lab, w, ar = (em.aux_index(name) if name else -1 for name in (ls.label, ls.weight, ls.area))
+        if ls.causal:
             # the residual's area slot carries exp(-tol * running loss) * area, written by ppsci_causal_weights
-            cw = aux_index(ls["causal"])
-            causal.append((len(loss_keys), lab, w, ar, cw))
+            cw = em.aux_index(ls.causal)
+            causal.append(CausalRow(len(loss_keys), lab, w, ar, cw))
             prog.n_aux = max(prog.n_aux, ar + 1)
             ar = cw
-        if ls.get("periodic"):
-            periodic.append((len(loss_keys), lab))
-        if outputs[key].kind == "couple":
-            if ls.get("kind", 0) != 0 or ls.get("causal") or ls.get("periodic") or ar >= 0 or w < 0:
+        if ls.periodic:
+            periodic.append(PeriodicRow(len(loss_keys), lab))
+        value = val[id(out)]
+        if out.kind == "couple":
+            if ls.kind != 0 or ls.causal or ls.periodic or ar >= 0 or w < 0:
                 raise NotImplementedError("a batch-coupled residual is lowered under MSELoss (no area column), with its row mask "
                                           "as the weight column")
-            couple_rows[outputs[key].name] = (len(loss_keys), w)
+            couple_rows[id(out)] = (len(loss_keys), w)
             # the term's difference d = lhs - M v - label is formed BY THE PROGRAM (the residual row then holds d, which is what
             # the transposed product of the reverse sweep needs: vbar = -M^T (2 scale w d))
             if lab >= 0:
-                prog.residual(prog.op(L.OP_SUB, val[id(outputs[key])], prog.ld_aux(lab)), -1, w, ar, ls.get("scale", 1.0), 0)
-                loss_keys.append(key)
-                continue
-        prog.residual(val[id(outputs[key])], lab, w, ar, ls.get("scale", 1.0), ls.get("kind", 0))
-        loss_keys.append(key)
+                value, lab = prog.op(L.OP_SUB, value, prog.ld_aux(lab)), -1
+        prog.residual(value, lab, w, ar, ls.scale, ls.kind)
+        loss_keys.append(ls.key)
     for name in extra_outputs:
         prog.residual(val[id(outputs[name])], -1, -1, -1, 0.0)
         loss_keys.append(name)
-    value_index = {k: val[id(v)] for k, v in outputs.items()}
-    low = Lowered(model, streams, prog, input_names, aux_names, loss_keys, value_index)
-    low.causal = causal
-    low.periodic = periodic
-    low.param_slots = sorted(param_slots)
-    if reduces:
-        # pass 1: the summands alone, one LINEAR term each (scale 1 / N_global for a mean): its "loss terms" ARE the reductions
-        p1 = hp.Program(rows, len(in_keys))
-        v1: Dict[int, int] = {}
-        emit(p1, _walk([r.args[0] for r in reduces]), v1)
-        coef = [1.0 / float(n_global) if r.op == "mean" else 1.0 for r in reduces]
-        for r, c in zip(reduces, coef):
-            p1.residual(v1[id(r.args[0])], -1, -1, -1, c, hp.LOSS_LINEAR)
-        # pass 3: the residual program again + one LINEAR term per summand whose seed is c_k x dL/dR_k (a device value, written
-        # by pass 2's block sums): with R held fixed, the gradient of  L(U, R) + sum_k Rbar_k c_k sum_p v_k(p)  w.r.t. U is
-        # the gradient of the reference's loss, in which R depends on every point
-        import copy
+    return loss_keys, causal, periodic, couple_rows
 
-        p3 = copy.deepcopy(prog)
-        if len(p3.res) + len(reduces) > L.MAX_RES:
-            raise NotImplementedError(f"{len(p3.res)} loss terms + {len(reduces)} batch reductions exceed the {L.MAX_RES} term "
-                                      "slots of one epilogue program")
-        for k, (r, c) in enumerate(zip(reduces, coef)):
-            p3.residual(val[id(r.args[0])], -1, -1, -1, c, hp.LOSS_LINEAR, scale_param=k + 1)
-        low.reductions = {"k": len(reduces), "p1": p1, "p3": p3}
-    if couples:
-        import copy
 
-        if any(c.name not in couple_rows for c in couples):
-            raise NotImplementedError("a batch-coupled output needs a loss term (it has no values outside its rows)")
-        # value program: v of every coupling into a row of a [C, N] buffer (scale-0 terms: values only)
-        pv = hp.Program(rows, len(in_keys))
-        vv: Dict[int, int] = {}
-        emit(pv, _walk([c.args[1] for c in couples]), vv)
-        for c in couples:
-            pv.residual(vv[id(c.args[1])], -1, -1, -1, 0.0)
-        # adjoint program: the residual program + one LINEAR term per coupling on v, weighted per point by
-        # vbar = -M^T (2 scale w r) (an aux column written between the launches): with rhs held fixed, the gradient of
-        # L(U, rhs) + sum_q vbar_q v_q  w.r.t. U is the gradient of the reference's loss, in which rhs = M v(U)
-        p3 = copy.deepcopy(prog)
-        if len(p3.res) + len(couples) > L.MAX_RES:
-            raise NotImplementedError(f"{len(p3.res)} loss terms + {len(couples)} batch couplings exceed the {L.MAX_RES} term slots")
-        items = []
-        for c in couples:
-            vb = aux_index(COUPLE_VBAR_PREFIX + c.name)
-            p3.n_aux = max(p3.n_aux, vb + 1)
-            p3.residual(val[id(c.args[1])], -1, vb, -1, 1.0, hp.LOSS_LINEAR)
-            row, w = couple_rows[c.name]
-            items.append({"name": c.name, "rows": c.comp[0], "cols": c.comp[1], "res_row": row, "weight_aux": w,
-                          "factor": 1.0 if c.value is None else c.value,
-                          "rhs_aux": aux_names.index(COUPLE_RHS_PREFIX + c.name), "vbar_aux": vb})
-        low.aux_names = aux_names
-        low.couplings = {"items": items, "pv": pv, "p3": p3}
-    # ---- stream programs of the input transforms: <= MAX_RES output rows per program, rows in (feature, stream) order
+def _reduction_plan(em: _Emitter, prog: hp.Program, val, reduces, n_global) -> ReductionPlan:
+    # pass 1: the summands alone, one LINEAR term each (scale 1 / N_global for a mean): its "loss terms" ARE the reductions
+    p1 = hp.Program(prog.n_streams, prog.n_in)
+    v1: Dict[int, int] = {}
+    em.emit(p1, _walk([r.args[0] for r in reduces]), v1)
+    coef = [1.0 / float(n_global) if r.op == "mean" else 1.0 for r in reduces]
+    for r, c in zip(reduces, coef):
+        p1.residual(v1[id(r.args[0])], -1, -1, -1, c, hp.LOSS_LINEAR)
+    # pass 3: the residual program again + one LINEAR term per summand whose seed is c_k x dL/dR_k (a device value, written
+    # by pass 2's block sums): with R held fixed, the gradient of  L(U, R) + sum_k Rbar_k c_k sum_p v_k(p)  w.r.t. U is
+    # the gradient of the reference's loss, in which R depends on every point
+    p3 = prog.copy()
+    if len(p3.res) + len(reduces) > L.MAX_RES:
+        raise NotImplementedError(f"{len(p3.res)} loss terms + {len(reduces)} batch reductions exceed the {L.MAX_RES} term "
+                                  "slots of one epilogue program")
+    for k, (r, c) in enumerate(zip(reduces, coef)):
+        p3.residual(val[id(r.args[0])], -1, -1, -1, c, hp.LOSS_LINEAR, scale_param=k + 1)
+    return ReductionPlan(len(reduces), p1, p3)
+
+
+def _coupling_plan(em: _Emitter, prog: hp.Program, val, couples, couple_rows) -> CouplingPlan:
+    if any(id(c) not in couple_rows for c in couples):
+        raise NotImplementedError("a batch-coupled output needs a loss term (it has no values outside its rows)")
+    # value program: v of every coupling into a row of a [C, N] buffer (scale-0 terms: values only)
+    pv = hp.Program(prog.n_streams, prog.n_in)
+    vv: Dict[int, int] = {}
+    em.emit(pv, _walk([c.args[1] for c in couples]), vv)
+    for c in couples:
+        pv.residual(vv[id(c.args[1])], -1, -1, -1, 0.0)
+    # adjoint program: the residual program + one LINEAR term per coupling on v, weighted per point by
+    # vbar = -M^T (2 scale w r) (an aux column written between the launches): with rhs held fixed, the gradient of
+    # L(U, rhs) + sum_q vbar_q v_q  w.r.t. U is the gradient of the reference's loss, in which rhs = M v(U)
+    p3 = prog.copy()
+    if len(p3.res) + len(couples) > L.MAX_RES:
+        raise NotImplementedError(f"{len(p3.res)} loss terms + {len(couples)} batch couplings exceed the {L.MAX_RES} term slots")
+    items = []
+    for c in couples:
+        name = em.couple_name[id(c)]
+        vb = em.aux_index(COUPLE_VBAR_PREFIX + name)
+        p3.n_aux = max(p3.n_aux, vb + 1)
+        p3.residual(val[id(c.args[1])], -1, vb, -1, 1.0, hp.LOSS_LINEAR)
+        row, w = couple_rows[id(c)]
+        items.append(Coupling(name, c.comp[0], c.comp[1], row, w, em.aux_names.index(COUPLE_RHS_PREFIX + name), vb,
+                              1.0 if c.value is None else c.value, c.matrix))
+    return CouplingPlan(tuple(items), pv, p3)
+
+
+def _feature_programs(em: _Emitter, features: Dict[int, list], n_in: int) -> Dict[int, list]:
+    """Stream programs of the input transforms: <= MAX_RES output rows per program, rows in (feature, stream) order."""
     pre = {}
-    for mid, blocks in pre_nets.items():
+    for mid, blocks in features.items():
         flat_rows = [e for rows_k in blocks for e in rows_k]
         progs = []
         for r0 in range(0, len(flat_rows), L.MAX_RES):
             chunk = flat_rows[r0:r0 + L.MAX_RES]
-            pg = hp.Program(0, len(in_keys))
+            pg = hp.Program(0, n_in)
             pval: Dict[int, int] = {}
-            emit_pointwise(pg, _walk(chunk), pval)
+            em.emit(pg, _walk(chunk), pval, pointwise=True)
             for e in chunk:
                 pg.residual(pval[id(e)], -1, -1, -1, 0.0)
             progs.append((pg, r0, len(chunk)))
         pre[mid] = progs
-    low.nets = [(mm, spec, r, idx, pre.get(id(mm))) for mm, spec, r, idx in nets]
-    return low
+    return pre
+
+
+def lower(outputs: Dict[str, Sym], losses: Sequence[LossTerm], extra_outputs: Sequence[str] = (),
+          n_global: Optional[int] = None, jet=None) -> Lowered:
+    """outputs: name -> traced expression.  Residual row k of the epilogue corresponds to losses[k]; `extra_outputs` are
+       appended as scale-0 residual rows so that eval / predict can read their values.
+       jet: the stream choice of a separable net (arch.spinn.JetTable) instead of the Taylor kernels' direction set: U row q is
+       the q-th distinct per-axis order triple the program reads, in order of first use; the program is emitted as for any
+       other model."""
+    losses = [ls if isinstance(ls, LossTerm) else LossTerm(**ls) for ls in losses]  # (callers that still pass key -> value rows)
+    roots = list(outputs.values())
+    nodes = _walk(roots)
+    if jet is not None:
+        _check_separable(nodes, losses, jet)
+    reduces, couples, model_list = _validate(nodes, roots, n_global)
+    plan = _plan_streams(nodes, model_list, jet)
+    slots, features = _net_slots([] if jet is not None else model_list, plan)
+    em = _Emitter(plan, slots, reduces, couples, jet)
+    prog = hp.Program(sum(len(s.model.output_keys) for s in slots) * plan.S, len(plan.in_keys))
+    val: Dict[int, int] = {}
+    em.emit(prog, nodes, val)
+    if jet is not None:
+        prog.n_streams = len(jet.orders)
+    loss_keys, causal, periodic, couple_rows = _emit_losses(em, prog, val, outputs, losses, extra_outputs)
+    param_slots = sorted(em.param_slots)
+    # (the aux columns are numbered in order of first use: residual program, loss terms, coupling adjoints, stream programs)
+    reductions = _reduction_plan(em, prog, val, reduces, n_global) if reduces else None
+    couplings = _coupling_plan(em, prog, val, couples, couple_rows) if couples else None
+    pre = _feature_programs(em, features, len(plan.in_keys))
+    return Lowered(model_list[0] if model_list else None, plan.streams, prog, em.input_names, em.aux_names, loss_keys,
+                   {k: val[id(v)] for k, v in outputs.items()}, [dataclasses.replace(s, pre=pre.get(id(s.model))) for s in slots],
+                   causal, periodic, param_slots, couplings, reductions)

@@ -508,6 +508,12 @@ class Program:
         self.n_aux = 0
         self._memo: Dict[Tuple, int] = {}
 
+    def copy(self) -> "Program":
+        """An independent program with the same instructions and terms (graph.lower: the adjoint passes extend one)."""
+        p = Program(self.n_streams, self.n_in)
+        p.instrs, p.res, p.n_aux, p._memo = list(self.instrs), list(self.res), self.n_aux, dict(self._memo)
+        return p
+
     def _emit(self, op, a=0, b=0, c=0.0, memo=True) -> int:
         key = (op, a, b, float(c))
         if memo and key in self._memo:

@@ -19,7 +19,7 @@ from . import hotpath as hp
 import os
 
 from .arch.spinn import GridLinear, JetTable
-from .compile import LABEL_PREFIX, WEIGHT_PREFIX
+from .compile import LABEL_PREFIX, WEIGHT_PREFIX, loss_terms
 from .engine import StepGraph, run_on_streams
 from .hotpath import _p, _stream_ptr
 
@@ -368,9 +368,7 @@ def jet_constraint(name, model, vals, label_keys, weight_keys, loss, device, wor
     for k, v in vals.items():
         v = v._as_sym() if hasattr(v, "_as_sym") else v
         outputs[k] = v if isinstance(v, graph.Sym) else graph._lift(v)
-    losses = [dict(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None, area=None,
-                   scale=1.0, kind=getattr(loss, "term_kind", 0), causal=(k if getattr(loss, "causal", None) else None),
-                   periodic=bool(getattr(loss, "periodic", False))) for k in label_keys]
+    losses = loss_terms(label_keys, weight_keys, loss, 0, scale=1.0)  # (the scales are set per bind: scale_fns)
     jet = JetTable(model)
     try:
         low = graph.lower(outputs, losses, extra_outputs, jet=jet)

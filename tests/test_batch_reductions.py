@@ -53,7 +53,7 @@ def test_mean_and_sum_inside_expressions(dev, tmp_path, reduction):
     }
     solver = _solver(tmp_path, model, exprs, inp, reduction)
     cc = solver._compiled["EQ"]
-    assert cc.low.reductions["k"] == 3 and not cc.fused.one_launch_ready()
+    assert cc.low.reductions.k == 3 and not cc.fused.one_launch_ready()
     solver.engine.forward_backward([cc.fused])
     losses = cc.fused.losses()
     grad = solver.engine.grad.detach().cpu().numpy().astype(np.float64)
@@ -108,14 +108,14 @@ def test_what_is_refused_says_why(dev):
 
     def lower(exprs):
         outs = cp.trace_exprs(model, ("x",), exprs, (), None, [])
-        return graph.lower(outs, [dict(key=k, label=None, weight=None, area=None, scale=1.0) for k in exprs], n_global=10)
+        return graph.lower(outs, [graph.LossTerm(key=k) for k in exprs], n_global=10)
 
     with pytest.raises(NotImplementedError, match="inside a batch reduction"):
         lower({"var": lambda d: ((d["u"] - d["u"].mean()) ** 2).mean()})
     with pytest.raises(NotImplementedError, match="differentiate first"):
         lower({"bad": lambda d: jacobian(d["u"].mean() * d["x"], d["x"])})
     low = lower({"ok": lambda d: d["u"] * d["x"].mean()})  # (a reduction of an input column is still a reduction: 1 slot)
-    assert low.reductions["k"] == 1
+    assert low.reductions.k == 1
 
 
 def test_volterra_coupled_residual_matches_autograd(dev, tmp_path):

@@ -34,34 +34,45 @@ def test_registration_order_matches_the_reference_for_elasticity():
         ppsci.equation.NormalDotVec(())
 
 
+def case_nlsmb():
+    return ppsci.arch.MLP(("t", "x"), ("Eu", "Ev", "pu", "pv", "eta"), 2, 16), ppsci.equation.NLSMB(0.5, -1, -1, True), ("t", "x")
+
+
+def case_elasticity():
+    disp = ppsci.arch.MLP(("x", "y", "z"), ("u", "v", "w"), 2, 16)
+    stress = ppsci.arch.MLP(("x", "y", "z"), ("sigma_xx", "sigma_yy", "sigma_zz", "sigma_xy", "sigma_xz", "sigma_yz"), 2, 16)
+    el = ppsci.equation.LinearElasticity(E=None, nu=None, lambda_=1e4, mu=100, dim=3)
+    keys = [k for k in el.equations if not k.startswith("traction")]
+    el.equations = {k: el.equations[k] for k in keys[:8]}  # (at most eight loss terms per constraint: the interior ones)
+    return ppsci.arch.ModelList((disp, stress)), el, ("x", "y", "z")
+
+
+def case_heat_exchanger():  # (the wall's network does not take the two mass flows)
+    hx = ppsci.arch.ModelList((ppsci.arch.MLP(("x", "t", "qm_h"), ("T_h",), 2, 16), ppsci.arch.MLP(("x", "t", "qm_c"), ("T_c",), 2, 16),
+                               ppsci.arch.MLP(("x", "t"), ("T_w",), 2, 16)))
+    return hx, ppsci.equation.HeatExchanger(1.0, 1.0, 1.0, 1.0, 1.0, 1.0), ("x", "t", "qm_h", "qm_c")
+
+
+def equation_exprs(model, eq):
+    return {k: ppsci.lambdify(v, model) if isinstance(v, sp.Basic) else v for k, v in eq.equations.items()}
+
+
 def test_new_equation_classes_lower_to_per_point_programs():
     from paddlescience_amd import compile as cp
     from paddlescience_amd import device, graph
-    from paddlescience_amd.compile import LABEL_PREFIX
 
     device.set_device("cpu")
     try:
         def lower(model, eq, inputs):
-            exprs = {k: ppsci.lambdify(v, model) if isinstance(v, sp.Basic) else v for k, v in eq.equations.items()}
+            exprs = equation_exprs(model, eq)
             outs = cp.trace_exprs(model, tuple(inputs), exprs, (), None, [])
-            loss = ppsci.loss.MSELoss("mean")
-            losses = [dict(key=k, label=LABEL_PREFIX + k, weight=None, area=None, scale=loss.term_scale(k, 64), kind=0, causal=None,
-                           periodic=False) for k in exprs]
-            return graph.lower(outs, losses, ())
+            return graph.lower(outs, cp.loss_terms(list(exprs), (), ppsci.loss.MSELoss("mean"), 64), ())
 
-        low = lower(ppsci.arch.MLP(("t", "x"), ("Eu", "Ev", "pu", "pv", "eta"), 2, 16), ppsci.equation.NLSMB(0.5, -1, -1, True), ("t", "x"))
+        low = lower(*case_nlsmb())
         assert low.program.build().n_res == 5 and low.streams.n2 >= 1  # E_tt: a second-order stream along t
-        disp = ppsci.arch.MLP(("x", "y", "z"), ("u", "v", "w"), 2, 16)
-        stress = ppsci.arch.MLP(("x", "y", "z"), ("sigma_xx", "sigma_yy", "sigma_zz", "sigma_xy", "sigma_xz", "sigma_yz"), 2, 16)
-        model = ppsci.arch.ModelList((disp, stress))
-        el = ppsci.equation.LinearElasticity(E=None, nu=None, lambda_=1e4, mu=100, dim=3)
-        keys = [k for k in el.equations if not k.startswith("traction")]
-        el.equations = {k: el.equations[k] for k in keys[:8]}  # (at most eight loss terms per constraint: the interior ones)
-        low = lower(model, el, ("x", "y", "z"))
+        low = lower(*case_elasticity())
         assert low.program.build().n_res == 8 and len(low.nets) == 2
-        hx = ppsci.arch.ModelList((ppsci.arch.MLP(("x", "t", "qm_h"), ("T_h",), 2, 16), ppsci.arch.MLP(("x", "t", "qm_c"), ("T_c",), 2, 16),
-                                   ppsci.arch.MLP(("x", "t"), ("T_w",), 2, 16)))
-        low = lower(hx, ppsci.equation.HeatExchanger(1.0, 1.0, 1.0, 1.0, 1.0, 1.0), ("x", "t", "qm_h", "qm_c"))
+        low = lower(*case_heat_exchanger())
         assert low.program.build().n_res == 3 and len(low.nets) == 3
     finally:
         device.set_device(None)

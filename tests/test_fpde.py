@@ -184,7 +184,6 @@ def _ref_loss_grad(model, eq, batch, n, dtype, device="cpu"):
 
 
 def _check_step(solver, eq, n, monkeypatch, tol_loss=2e-5, tol_grad=5e-5, ref_device="cpu"):
-    from paddlescience_amd import graph
     from paddlescience_amd import hotpath as hp
 
     calls = []
@@ -192,12 +191,16 @@ def _check_step(solver, eq, n, monkeypatch, tol_loss=2e-5, tol_grad=5e-5, ref_de
     monkeypatch.setattr(hp, "csr_matvec", lambda *a, **k: (calls.append(k.get("xscale") is not None), real(*a, **k))[1])
     cc = solver._compiled["FPDE"]
     assert cc.low.couplings and any("fractional_poisson_matrix" in s for s in cc.specialised_to)
-    (it,), (M,) = cc.low.couplings["items"], cc.fused.couplings["M"]
+    (it,), (M,) = cc.low.couplings.items, cc.fused.couplings["M"]
     # the sparse path: device CSR of M and M^T, no dense [N, batch] matrix anywhere
     assert isinstance(M, dict) and M["M"]["vals"].numel() == eq.int_mat.nnz == M["MT"]["vals"].numel()
-    assert it["name"] not in graph._COUPLE_MATS
+    # the host matrix went to the device and was let go: no record of the constraint still holds it
+    assert it.matrix is None and all(c.matrix is None for c in cc.fused.couplings["items"])
+    for m, dev_m in ((eq.int_mat, M["M"]), (eq.int_mat.transpose(), M["MT"])):
+        for f in ("row_ptr", "col_idx", "vals"):
+            assert np.array_equal(dev_m[f].cpu().numpy(), getattr(m, f)), f
     big = [t for t in list(M["M"].values()) + list(M["MT"].values()) if isinstance(t, torch.Tensor)]
-    assert all(t.numel() < n * it["cols"] for t in big)
+    assert all(t.numel() < n * it.cols for t in big)
     solver.engine.forward_backward([cc.fused])
     assert sorted(set(calls)) == [False, True]  # forward product and the transposed one, both through ppsci_csr_matvec
     loss = cc.fused.losses()["fpde"]

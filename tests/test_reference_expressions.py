@@ -17,7 +17,6 @@ import pytest
 import ppsci
 from paddlescience_amd import compile as cp
 from paddlescience_amd import device, graph
-from paddlescience_amd.compile import LABEL_PREFIX
 from ppsci.autodiff import hessian, jacobian
 
 
@@ -40,9 +39,7 @@ def _lower(model, exprs, input_keys, label_keys=None, batch=None):
         if k not in outputs:
             outputs[k] = graph.Sym.net(model, model.output_keys.index(k))
     # (a batch-coupled output carries its row mask as the weight column: compile.CompiledConstraint adds it)
-    losses = [dict(key=k, label=LABEL_PREFIX + k, weight=(cp.WEIGHT_PREFIX + k) if outputs[k].kind == "couple" else None, area=None,
-                   scale=loss.term_scale(k, 100), kind=0, causal=None, periodic=False) for k in label_keys]
-    low = graph.lower(outputs, losses, ())
+    low = graph.lower(outputs, cp.loss_terms(label_keys, [k for k in label_keys if outputs[k].kind == "couple"], loss, 100), ())
     return low.program.build(), low.streams
 
 
@@ -223,6 +220,31 @@ def test_inventory_has_no_unexplained_raises(capsys):
     for ex, st, det in rows:
         if st == "raises":  # the one structural case of the module docstring: nothing else may fail
             assert "input transform" in det, (ex, det)
+
+
+def test_a_dropped_trace_takes_its_nodes_and_its_model_with_it():
+    """The hash-cons table holds its nodes weakly: once the model, the traced outputs and the Lowered are gone, so is every
+    `net` node of the trace (each holds the model) and the model itself.  (Counted against whatever else is alive in the
+    process, so that the check does not depend on which tests ran before it.)"""
+    import gc
+    import weakref
+
+    def net_nodes():
+        return [n for n in list(graph.Sym._cache.values()) if n.kind == "net"]
+
+    ppsci.autodiff.clear()
+    gc.collect()
+    before = len(net_nodes())
+    m = _mlp(("x", "y"), ("u_probe",))
+    exprs = {"r": lambda d: hessian(d["u_probe"], d["x"]) + jacobian(d["u_probe"] * d["y"], d["y"])}
+    outputs = cp.trace_exprs(m, ("x", "y"), exprs, (), None, [])
+    low = graph.lower(outputs, cp.loss_terms(["r"], (), ppsci.loss.MSELoss("mean"), 8), ())
+    assert low.nets[0].model is m and len(net_nodes()) >= before + 3  # u, u_xx, u_y
+    alive = weakref.ref(m)
+    del m, exprs, outputs, low
+    gc.collect()
+    assert alive() is None
+    assert len(net_nodes()) <= before and not any("u_probe" in n.model.output_keys for n in net_nodes())
 
 
 def test_third_order_mixed_derivative_values(tmp_path):

@@ -9,9 +9,11 @@ from tests.spinn_jet_cases import KEYS, closures, constraint, make_model, solver
 dev = make_dev_fixture()
 
 
-def _lower(model, expr):
+def lowered(model, expr):
+    """(Lowered, JetTable) of one residual under a weighted label."""
     from paddlescience_amd import graph
     from paddlescience_amd.arch.spinn import JetTable
+    from paddlescience_amd.compile import loss_terms
     from paddlescience_amd.graph import Sym
 
     data = {k: Sym.input(k) for k in KEYS}
@@ -19,7 +21,11 @@ def _lower(model, expr):
     v = expr(data)
     v = v._as_sym() if hasattr(v, "_as_sym") else v
     jet = JetTable(model)
-    low = graph.lower({"e": v}, [dict(key="e", label="label:e", weight="weight:e", scale=1.0)], jet=jet)
+    return graph.lower({"e": v}, loss_terms(["e"], ["e"], None, 0, scale=1.0), jet=jet), jet
+
+
+def _lower(model, expr):
+    low, jet = lowered(model, expr)
     return low.program.instrs, low.program.res, jet.orders, low.aux_names
 
 

@@ -9,7 +9,7 @@ every wave evaluates redundantly for its own lanes -- no serial wave, no second 
 plan matches a program against these tables word for word (structure only: the constants' VALUES stay run-time data, so
 one table serves AllenCahn(eps) for every eps); a program that matches none runs on the VM as before.
 
-Every table below is produced by running the SAME lowering the API path uses (compile.trace_exprs + graph.lower on the
+Every table below is produced by running the SAME lowering the API path uses (compile.lower_constraint on the
 package's equation classes) or the same hand-built hp.Program the bench / tests use, then pre-decoding it exactly as
 csrc/epilogue_vm.h epi_fast_encode does (tests/test_static_programs.py checks this port against the C function and
 that the committed header is what this script generates).
@@ -81,20 +81,11 @@ def predecode(e):
 
 # ---------------------------------------------------------------------------------------------- the programs
 def _lower(model, exprs, input_keys, label_keys, weight_keys=()):
-    """What compile.CompiledConstraint does for an MSE constraint, without device buffers."""
+    """The device-free half of a compile.CompiledConstraint under MSELoss (a batch of 1000: the scales are run-time data)."""
     import paddlescience_amd as ppsci
     from paddlescience_amd import compile as cp
-    from paddlescience_amd import graph
-    from paddlescience_amd.compile import LABEL_PREFIX, WEIGHT_PREFIX
 
-    loss = ppsci.loss.MSELoss("mean")
-    outputs = cp.trace_exprs(model, input_keys, exprs, (), None, [])
-    for k in label_keys:
-        if k not in outputs:
-            outputs[k] = graph.Sym.net(model, model.output_keys.index(k))
-    losses = [dict(key=k, label=LABEL_PREFIX + k, weight=(WEIGHT_PREFIX + k) if k in weight_keys else None, area=None,
-                   scale=loss.term_scale(k, 1000), kind=0, causal=None, periodic=False) for k in label_keys]
-    low = graph.lower(outputs, losses, ())
+    low = cp.lower_constraint(model, exprs, input_keys, label_keys, weight_keys, ppsci.loss.MSELoss("mean"), 1000, 1000).low
     return low.program.build(), low.streams
 
 
